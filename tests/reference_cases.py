@@ -1124,3 +1124,127 @@ def by_name(name):
         if c.name == name:
             return c
     raise KeyError(name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# checks that run the reference live where it exists; tests/golden/reference_checks.npz holds what it returned, so the
+# same checks run on a machine without the reference checkout (tests/golden/make_golden_from_reference.py writes it)
+# ---------------------------------------------------------------------------------------------------------------------
+REFERENCE_FILES = ("nn/kernel/map_reduce.py", "nn/kernel/segment.py", "nn/conv/gcn.py", "nn/conv/gat.py",
+                   "nn/conv/graph_sage.py", "utils/graph_utils.py", "layers/conv/gcn.py", "layers/conv/gat.py",
+                   "layers/conv/graph_sage.py")
+FUZZ_SEEDS = range(6)
+NUM_SPLITS_F = (1, 7, 12, 100, 128, 602, 1433)
+NUM_SPLITS_K = (None, 1, 2, 3, 4, 5, 7, 8, 16, 100)
+
+
+def inputs_digest(value):
+    """sha256 of a case's inputs (arrays by dtype, shape and bytes; generators by their state): names the exact inputs the
+    committed golden vectors were computed from."""
+    import hashlib
+    import json
+    h = hashlib.sha256()
+
+    def walk(v):
+        if isinstance(v, dict):
+            h.update(b"{")
+            for k in sorted(v):
+                h.update(repr(k).encode())
+                walk(v[k])
+            h.update(b"}")
+        elif isinstance(v, (list, tuple)):
+            h.update(b"[")
+            for x in v:
+                walk(x)
+            h.update(b"]")
+        elif isinstance(v, np.ndarray):
+            h.update("{}{}".format(v.dtype.str, v.shape).encode())
+            h.update(np.ascontiguousarray(v).tobytes())
+        elif isinstance(v, np.random.Generator):
+            h.update(json.dumps(v.bit_generator.state, sort_keys=True).encode())
+        else:
+            h.update(repr(v).encode())
+    walk(value)
+    return h.hexdigest()
+
+
+def fuzz_check_inputs(seed):
+    """Fresh graph (duplicates, self-loops, isolated nodes) and parameters of one seed of the oracle-vs-live-reference fuzz."""
+    g = graph(60 + 17 * seed, 400 + 90 * seed, 5 + seed, seed=900 + seed, self_loops=seed, isolated=seed % 3)
+    rng = g["rng"]
+    f, u = g["x"].shape[1], 4 + seed
+    p = dict(g, f=f, u=u, cfg=NORM_CFGS[seed % len(NORM_CFGS)], normalize=bool(seed % 2))
+    p["kernel"], p["bias"] = glorot(rng, f, u), small_bias(rng, u)
+    H = [1, 2, 4, 8, 2, 4][seed]
+    A, U = H * (1 + seed % 3), H * 3
+    p["H"] = H
+    p["wq"], p["wk"], p["wv"] = glorot(rng, f, A), glorot(rng, f, A), glorot(rng, f, U)
+    p["bq"], p["bk"], p["b"] = small_bias(rng, A), small_bias(rng, A), small_bias(rng, U)
+    p["ws"], p["wn"], p["b2"] = glorot(rng, f, u), glorot(rng, f, u), small_bias(rng, 2 * u)
+    p["s"] = (rng.standard_normal(g["ei"].shape[1]) * 4).astype(np.float32)
+    return p
+
+
+def fuzz_check_ref(R, p):
+    nn, tf = R.tfg.nn, R.tf
+    x, ei, w, n = p["x"], p["ei"], p["w"], p["n"]
+    out = {}
+    for red in ("sum", "mean", "max"):
+        out["aggregate-" + red] = nn.aggregate_neighbors(x, ei, w, R.tfg.nn.conv.gcn.gcn_mapper, getattr(nn, red + "_reducer"),
+                                                         nn.identity_updater).numpy()
+    adj = R.tfs.SparseMatrix(ei, w, [n, n])
+    out["gcn"] = nn.gcn(x, adj, p["kernel"], p["bias"], activation=tf.nn.relu, **p["cfg"]).numpy()
+    out["gat"] = nn.gat(x, ei, p["wq"], p["bq"], tf.nn.relu, p["wk"], p["bk"], tf.nn.relu, p["wv"], p["b"], tf.nn.relu,
+                        num_heads=p["H"]).numpy()
+    for name in ("mean", "sum"):
+        out[name + "-sage"] = getattr(nn, name + "_graph_sage")(x, ei, w, p["ws"], p["wn"], p["b2"], tf.nn.relu,
+                                                                normalize=p["normalize"]).numpy()
+    out["segment_softmax"] = R.tfg.nn.kernel.segment.segment_softmax(p["s"], ei[0], n).numpy()
+    return out
+
+
+def fuzz_check_orc(o, p):
+    x, ei, w, n = p["x"], p["ei"], p["w"], p["n"]
+    out = {}
+    for red in ("sum", "mean", "max"):
+        out["aggregate-" + red] = o.aggregate_neighbors(x, ei, w, o.gcn_mapper, getattr(o, red + "_reducer"),
+                                                        o.identity_updater)
+    out["gcn"] = o.gcn(x, ei, w, p["kernel"], p["bias"], "relu", **p["cfg"])
+    out["gat"] = o.gat(x, ei, p["wq"], p["bq"], "relu", p["wk"], p["bk"], "relu", p["wv"], p["b"], "relu", num_heads=p["H"])
+    for name in ("mean", "sum"):
+        out[name + "-sage"] = getattr(o, name + "_graph_sage")(x, ei, w, p["ws"], p["wn"], p["b2"], "relu",
+                                                               normalize=p["normalize"])
+    out["segment_softmax"] = o.segment_softmax(p["s"], ei[0], n)
+    return out
+
+
+def num_splits_table(fn):
+    """[[f, k, split sizes or "raises"], ...] of compute_num_or_size_splits over the grid."""
+    rows = []
+    for f in NUM_SPLITS_F:
+        for k in NUM_SPLITS_K:
+            try:
+                got = fn(f, k)
+            except Exception:
+                got = "raises"
+            if isinstance(got, (list, tuple)):
+                got = [int(v) for v in got]
+            elif got is not None and not isinstance(got, str):
+                got = int(got)
+            rows.append([f, k, got])
+    return rows
+
+
+def check_loaded_unmodified(tfg, root):
+    """The package the harness loaded is the one under `root`, and each of REFERENCE_FILES is imported byte for byte as
+    it lies on disk there."""
+    import hashlib
+    import importlib
+    import os
+    assert os.path.realpath(tfg.__file__).startswith(os.path.realpath(root)), tfg.__file__
+    for rel in REFERENCE_FILES:
+        m = importlib.import_module("tf_geometric." + rel[:-3].replace("/", "."))
+        with open(os.path.join(root, "tf_geometric", rel), "rb") as f:
+            on_disk = hashlib.sha1(f.read()).hexdigest()
+        with open(m.__file__, "rb") as f:
+            assert hashlib.sha1(f.read()).hexdigest() == on_disk, rel

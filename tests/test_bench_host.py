@@ -61,3 +61,16 @@ def test_a_stale_error_lock_of_an_earlier_job_does_not_silence_the_watchdog(tmp_
     # the SAME job's second rank (same launcher, same port) finds the first one's file and stays quiet
     res2 = _run(["--workload", "tiny", "--gpus", "2"], dict(env, RANK="0", LOCAL_RANK="0"))
     assert res2.returncode == 3 and res2.stdout.decode().strip() == ""
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: every row of a small output; of a large one a sorted, seeded sample that is the same in every call
+    (so two builds dump the same rows) and stays inside the budget together with its float64 node ids."""
+    import numpy as np
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.dump_rows(20000, 100), np.arange(20000))
+    a, b = bench.dump_rows(2400000, 100), bench.dump_rows(2400000, 100)
+    assert np.array_equal(a, b) and a.size * (4 * 100 + 8) <= bench.DUMP_BYTES <= 64 << 20
+    assert a.size > 10000 and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 2400000

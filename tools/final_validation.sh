@@ -7,7 +7,7 @@ ROOT="$(pwd)"; OUT="$ROOT/gpurun_out/$NAME"; mkdir -p "$OUT"; export TMPDIR=/tmp
 python __graft_entry__.py --smoke > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log" >&2
 timeout 2000 python -m pytest tests -m gpu -x -q --durations=5 > "$OUT/pytest_gpu.log" 2>&1
 grep -n "passed\|failed" "$OUT/pytest_gpu.log" | tail -2 >&2
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

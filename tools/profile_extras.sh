@@ -7,7 +7,7 @@ OUT="$ROOT/gpurun_out/prof_r04"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/extras" -- python "$ROOT/bench.py" --extras --no-cpu-baseline --no-rmat --steps 5 --warmup 2 > "$OUT/bench_extras_under_stats.json" 2> "$OUT/extras.err"
+rocprofv3 --kernel-trace --stats -d "$OUT/extras" -- python "$ROOT/bench.py" --full --extras --no-cpu-baseline --no-rmat --steps 5 --warmup 2 > "$OUT/bench_extras_under_stats.json" 2> "$OUT/extras.err"
 rocprofv3 --kernel-trace --stats -d "$OUT/reddit" -- python "$ROOT/tools/bench_sweep.py" --only=reddit > "$OUT/reddit.jsonl" 2> "$OUT/reddit.err"
 cd "$ROOT"
 E=$(find "$OUT/extras" -name "*_results.db" | head -1)

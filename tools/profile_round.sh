@@ -12,8 +12,8 @@ cd /tmp
 HEAD="seg_reduce_kernel<4, 32, 1, false, true, false, false, 0>"
 TAIL="seg_reduce_kernel<4, 32, 1, false, true, true, false, 0>"
 # the whole default command (headline + static layout + R-MAT + configs block; CPU legs skipped: they launch nothing)
-rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/bench_under_stats.json" 2> "$OUT/stats.err"
-B="python $ROOT/bench.py --no-cpu-baseline --no-rmat --no-configs"
+rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/bench_under_stats.json" 2> "$OUT/stats.err"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-rmat --no-configs"
 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -- $B --steps 3 --warmup 1 > /dev/null 2> "$OUT/fetch.err"
 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -- $B --steps 3 --warmup 1 > /dev/null 2> "$OUT/write.err"
 cd "$ROOT"
@@ -33,8 +33,8 @@ python tools/make_pmc_json.py "$F" "$W" "$S2" "$HEAD" "$OUT/${TAG}_products_pmc.
 python tools/make_pmc_json.py "$F" "$W" "$S2" "$TAIL" "$OUT/${TAG}_products_edge_tail_pmc.json" products
 rm -rf "$OUT/stats" "$OUT/stats2" "$OUT/fetch" "$OUT/write"
 # the plain default line (what the driver runs) and the extras, unprofiled
-timeout 600 python bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench_products.json" 2> "$OUT/bench.err"
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-rmat --no-configs --extras > "$OUT/${TAG}_bench_extras.json" 2>> "$OUT/bench.err"
-timeout 600 python bench.py --workload arxiv --steps 50 --warmup 10 --extras > "$OUT/${TAG}_bench_arxiv_extras.json" 2>> "$OUT/bench.err"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench_products.json" 2> "$OUT/bench.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-rmat --no-configs --extras > "$OUT/${TAG}_bench_extras.json" 2>> "$OUT/bench.err"
+timeout 600 python bench.py --full --workload arxiv --steps 50 --warmup 10 --extras > "$OUT/${TAG}_bench_arxiv_extras.json" 2>> "$OUT/bench.err"
 ls -la "$OUT"
 tail -3 "$OUT/bench.err"

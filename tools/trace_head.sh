@@ -3,7 +3,7 @@
 set -u
 ROOT="$(pwd)"; TAG="${TFGX_ROUND:-r06}"; OUT="$ROOT/gpurun_out/${TAG}_trace_head"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
-timeout 170 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/${TAG}_bench_under_rocprof_head.json" 2> "$OUT/stats.err"
+timeout 170 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/${TAG}_bench_under_rocprof_head.json" 2> "$OUT/stats.err"
 cd "$ROOT"
 S=$(find "$OUT/stats" -name "*_results.db" -printf "%s %p\n" | sort -nr | head -1 | cut -d" " -f2-)
 python tools/rocpd_summary.py "$S" > "$OUT/${TAG}_rocprof_head.md"
