@@ -10,7 +10,8 @@
  *   - every pointer is a DEVICE pointer owned by the caller unless it says "host";
  *   - nothing is allocated here: outputs and workspaces are caller buffers;
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), except
- *     tfgx_build_csr_by_dst and tfgx_segment_topk, which synchronise once to report bad indices;
+ *     tfgx_build_csr_by_dst, tfgx_segment_topk and tfgx_induced_subgraph_count, which synchronise once to report
+ *     bad indices (the last also to return its output size);
  *   - return value: 0 = ok, otherwise a TFGX_ERR_* code; text via tfgx_last_error();
  *   - results are deterministic (no floating-point atomics anywhere);
  *   - index convention of the reference: edge_index[0] = row = DESTINATION (aggregating node),
@@ -619,6 +620,46 @@ size_t tfgx_segment_topk_workspace_bytes(int64_t n, int64_t num_segments);
 int tfgx_segment_topk(const int32_t* segment, const float* score, int64_t n, int64_t num_segments, int32_t k,
                       float ratio, int32_t* out_index, int32_t* out_count, void* workspace, size_t workspace_bytes,
                       tfgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Node-induced subgraph (BatchGraph.sample_new_graph_by_node_index, tf_geometric/data/graph.py:276-359, with
+ * compute_edge_mask_by_node_index, utils/graph_utils.py:538-551): the coarsening step of SAGPool / SortPool.
+ * Edge e = (row[e], col[e]) survives when both endpoints are in node_index[m]; node v becomes node_map[v] = its
+ * position in node_index (-1: dropped).  Two calls sharing one workspace of
+ * tfgx_induced_subgraph_workspace_bytes(n, E, m, with_plan) bytes:
+ *   _count : builds node_map[n], counts the kept edges, and SYNCHRONISES ONCE to return their number in *n_kept (host).
+ *            A duplicate or an id outside [0, n) in node_index -> TFGX_ERR_INVALID_ARG; an edge endpoint outside [0, n)
+ *            -> TFGX_ERR_INDEX.  Detected on the device, reported by the same device -> host read.
+ *   _emit  : (after a successful _count, same arguments, n_kept = its result) writes the n_kept surviving edges in their ORIGINAL order,
+ *            relabelled: out_row / out_col, and out_edge_id = the original id of each (gather edge attributes with
+ *            tfgx_permute_rows_f32).  With a parent CSR plan of the same edge list (tfgx_build_csr_by_dst output;
+ *            parent_row_ptr non-NULL, with_plan = 1 in the workspace query) it also writes the pooled graph's plan
+ *            out_row_ptr[m + 1], out_plan_col[n_kept], out_plan_perm[n_kept] WITHOUT sorting, bit-identical to
+ *            tfgx_build_csr_by_dst of (out_row, out_col) with n_dst = n_src = m.  Asynchronous.
+ * Deterministic: order-stable compaction, integer atomics only for the node flags.
+ * ------------------------------------------------------------------------------------------- */
+size_t tfgx_induced_subgraph_workspace_bytes(int64_t n, int64_t E, int64_t m, int32_t with_plan);
+int tfgx_induced_subgraph_count(const int32_t* row, const int32_t* col, int64_t E, int64_t n, const int32_t* node_index,
+                                int64_t m, int32_t* node_map /* [n] */, int64_t* n_kept /* host */, void* workspace,
+                                size_t workspace_bytes, tfgx_stream_t stream);
+int tfgx_induced_subgraph_emit(const int32_t* row, const int32_t* col, int64_t E, int64_t n, const int32_t* node_index,
+                               int64_t m, const int32_t* node_map, int64_t n_kept /* from _count */,
+                               const int32_t* parent_row_ptr /* or NULL */,
+                               const int32_t* parent_col, const int32_t* parent_perm, int32_t* out_row, int32_t* out_col,
+                               int32_t* out_edge_id, int32_t* out_row_ptr /* or NULL */, int32_t* out_plan_col,
+                               int32_t* out_plan_perm, void* workspace, size_t workspace_bytes, tfgx_stream_t stream);
+/* dst[i] = src[idx[i]] for i in [0, M) (node-graph ids of the kept nodes) */
+int tfgx_gather_i32(const int32_t* src, const int32_t* idx, int64_t M, int32_t* dst, tfgx_stream_t stream);
+/* out[i, :] = x[idx[i], :] * s[idx[i]] for i in [0, M) (SAGPool's x * score then gather, sag_pool.py:38-44: one product
+   per element, so the same bits); s == NULL: a plain row gather (SortPool).  16-byte accesses when ldx / ldo allow. */
+int tfgx_gather_scale_rows_f32(const float* x, int64_t ldx, const int32_t* idx, const float* s /* [n] or NULL */,
+                               int64_t M, int64_t F, float* out, int64_t ldo, tfgx_stream_t stream);
+/* Backward of tfgx_gather_scale_rows_f32 over ALL n parent rows, j = node_map[o] (tfgx_induced_subgraph_count output):
+   dx[o, :] = j >= 0 ? g[j, :] * s[o] : 0 (s == NULL: * 1);  ds[o] = j >= 0 ? sum_f g[j, f] * x[o, f] : 0.
+   dx or ds may be NULL.  One wave per row, fixed-order reduction: bit-reproducible, no atomics, no memset. */
+int tfgx_gather_scale_rows_backward_f32(const float* g, int64_t ldg, const int32_t* node_map, int64_t n, const float* x,
+                                        int64_t ldx, const float* s /* or NULL */, int64_t F, float* dx /* or NULL */,
+                                        int64_t lddx, float* ds /* or NULL */, tfgx_stream_t stream);
 
 /* x[n, F] -> x_main[n, f_main] + x_tail[n, F - f_main] in one pass (the split source layout of tfgx_reduce_args) */
 int tfgx_split_rows_f32(const float* x, int64_t ldx, int64_t n, int64_t F, int64_t f_main, float* x_main,

@@ -1,0 +1,341 @@
+# coding=utf-8
+"""SAGPool / SortPool / the induced-subgraph kernel on the GPU: parity with the reference's own outputs
+(tests/golden/pool_cases.npz), the derived CSR plan against a rebuilt one, gradients against float64 torch autograd on the
+CPU, determinism, invalid node lists, hipGraph refusal, and a few training steps of the hierarchical SAGPool model."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT, assert_parity
+import pool_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "pool_cases.npz")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return dict(np.load(GOLDEN))
+
+
+# ---- parity with the reference ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
+def test_hip_matches_reference_golden(case, tfg, golden):
+    got = case.hip(tfg, case.inputs())
+    keys = [k[len(case.name) + 2:] for k in golden if k.startswith(case.name + "::") and not k.endswith("__")]
+    assert keys
+    for k in keys:
+        ref = golden[case.name + "::" + k]
+        if k not in got:
+            # edge_weight=None stays None here; the reference's BatchGraph fills in ones (data/graph.py:50-56), which
+            # every consumer treats exactly like "no weight"
+            assert k.endswith("edge_weight") and np.array_equal(ref, np.ones_like(ref)), k
+            continue
+        a = np.asarray(got[k])
+        assert a.shape == ref.shape and a.dtype == ref.dtype, "{} {} {} vs {} {}".format(k, a.shape, a.dtype, ref.shape,
+                                                                                          ref.dtype)
+        if k in case.exact or a.dtype.kind in "iub":
+            assert np.array_equal(a, ref), "{}::{} must be bit-identical to the reference".format(case.name, k)
+        else:
+            assert_parity(a, ref, tol=case.tol, what="{}::{}".format(case.name, k))
+
+
+def test_tensor_inputs_give_tensor_outputs(tfg):
+    g = pc.batch()
+    dev = torch.device("cuda")
+    res = tfg.nn.sort_pool(torch.from_numpy(g["x"]).to(dev), torch.from_numpy(g["ei"]).to(dev), None,
+                           torch.from_numpy(g["gid"]).to(dev), k=3)
+    assert all(isinstance(t, torch.Tensor) for t in (res[0], res[1], res[3])) and res[2] is None
+    ref = tfg.nn.sort_pool(g["x"], g["ei"], None, g["gid"], k=3)
+    assert np.array_equal(res[1].cpu().numpy(), ref[1]) and np.array_equal(res[0].cpu().numpy(), ref[0])
+
+
+# ---- the derived plan --------------------------------------------------------------------------------------------------
+def _random_graph(n, e, seed, dev):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    ei = np.stack([rng.integers(0, n, e), rng.integers(0, n, e)]).astype(np.int32)
+    ei[:, : e // 20] = ei[0, : e // 20]         # some self-loops
+    ei[:, e // 20: e // 10] = ei[:, : e // 20][:, : e // 10 - e // 20]    # duplicates
+    keep = rng.permutation(n)[: n // 2].astype(np.int32)
+    return torch.from_numpy(ei).to(dev), torch.from_numpy(keep).to(dev)
+
+
+def _np_induced(ei, keep, n):
+    """numpy restatement of data/graph.py:322-351: mask, boolean_mask, relabel by position in keep."""
+    node_map = np.full(n, -1, np.int64)
+    node_map[keep] = np.arange(keep.size)
+    mask = (node_map[ei[0]] >= 0) & (node_map[ei[1]] >= 0)
+    return np.stack([node_map[ei[0][mask]], node_map[ei[1][mask]]]).astype(np.int32), np.flatnonzero(mask)
+
+
+@pytest.mark.parametrize("n,e", [(1, 0), (50, 0), (200, 400), (3000, 12000), (2000, 80000), (70000, 300000)])
+def test_derived_plan_equals_rebuilt_plan(tfg, n, e):
+    """short rows (8 lanes a row) and long rows (a wave a row): row_ptr / col / perm bit-identical to CsrPlan.build of
+    the pooled edge list; the pooled list exact against the numpy restatement."""
+    from tf_geometric_amd.utils.subgraph import induced_subgraph
+    dev = torch.device("cuda")
+    ei, keep = _random_graph(n, e, seed=n + e, dev=dev)
+    parent = tfg.CsrPlan.build(ei, n)
+    sub = induced_subgraph(ei, keep, n, parent_plan=parent)
+    ref_ei, ref_id = _np_induced(ei.cpu().numpy(), keep.cpu().numpy(), n)
+    assert np.array_equal(sub.edge_index.cpu().numpy(), ref_ei)
+    assert np.array_equal(sub.edge_id.cpu().numpy(), ref_id)
+    m = int(keep.shape[0])
+    rebuilt = tfg.CsrPlan.build(sub.edge_index, m)
+    for a in ("row_ptr", "col", "perm"):
+        assert torch.equal(getattr(sub.plan, a), getattr(rebuilt, a)), a
+
+
+def test_derived_plan_products_shape(tfg):
+    """N = 2.4 M, E = 123 M (synthetic_edges), ratio 0.5 per graph of 64 contiguous blocks."""
+    from tf_geometric_amd.synthetic import synthetic_edges
+    from tf_geometric_amd.utils.subgraph import induced_subgraph
+    n, e = 2449029, 123718280
+    dev = torch.device("cuda")
+    ei_np = synthetic_edges(n, e, seed=0)
+    ei = torch.from_numpy(ei_np).to(dev)
+    gid = (torch.arange(n, device=dev, dtype=torch.int64) * 64 // n).to(torch.int32)
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    score = torch.rand(n, generator=gen).to(dev)
+    keep = tfg.nn.topk_pool(gid, score, ratio=0.5)
+    parent = tfg.CsrPlan.build(ei, n)
+    sub = induced_subgraph(ei, keep, n, parent_plan=parent)
+    ref_ei, _ = _np_induced(ei_np, keep.cpu().numpy(), n)
+    assert np.array_equal(sub.edge_index.cpu().numpy(), ref_ei)
+    del ref_ei
+    rebuilt = tfg.CsrPlan.build(sub.edge_index, int(keep.shape[0]))
+    for a in ("row_ptr", "col", "perm"):
+        assert torch.equal(getattr(sub.plan, a), getattr(rebuilt, a)), a
+
+
+def test_sampler_plan_equals_rebuilt_plan(tfg):
+    """The plan RandomNeighborSampler attaches (now used by SparseMatrix.plan as well) is bit-identical to a rebuild:
+    existing outputs do not change."""
+    dev = torch.device("cuda")
+    ei, _ = _random_graph(3000, 30000, seed=9, dev=dev)
+    sampler = tfg.utils.RandomNeighborSampler(ei)
+    for kw in (dict(k=5), dict(ratio=0.5), dict(k=4, sampled_node_index=torch.arange(0, 3000, 3, device=dev))):
+        sei, _ = sampler.sample(seed=3, **kw)
+        att = sei._tfgx_plan
+        rebuilt = tfg.CsrPlan.build(sei, att.n_dst, att.n_src)
+        for a in ("row_ptr", "col", "perm"):
+            assert torch.equal(getattr(att, a), getattr(rebuilt, a)), a
+        n = att.n_dst
+        adj = tfg.SparseMatrix(sei, None, [n, max(n, att.n_src)])
+        assert adj.plan.col is att.col          # consulted, not rebuilt
+
+
+def test_pooled_edge_index_carries_its_plan(tfg):
+    g = pc.batch()
+    dev = torch.device("cuda")
+    x, ei, gid = (torch.from_numpy(g[k]).to(dev) for k in ("x", "ei", "gid"))
+    px, pei, pw, pgi = tfg.nn.sag_pool(x, ei, None, gid, lambda inp, training=None: torch.from_numpy(g["score"]).to(dev),
+                                       ratio=0.5)
+    plan = pei._tfgx_plan
+    m = int(px.shape[0])
+    assert plan.n_dst == m and plan.num_edges == int(pei.shape[1])
+    assert tfg.SparseMatrix(pei, None, [m, m]).plan is plan
+    assert tfg.CsrPlan.from_cache(pei, m) is plan
+    t = plan.transposed()
+    rebuilt = tfg.CsrPlan.build(torch.stack([pei[1], pei[0]]), m)
+    assert torch.equal(t.perm, rebuilt.perm)
+
+
+# ---- gradients ---------------------------------------------------------------------------------------------------------
+def _gcn64(x, ei, w, kernel, bias, n):
+    """GCN (norm both, self-loops, renorm, sym) as float64 torch ops on the CPU: nn/conv/gcn.py:32-130, 225-290."""
+    row, col = ei[0].long(), ei[1].long()
+    w = torch.ones(row.shape[0], dtype=torch.float64) if w is None else w
+    deg = torch.zeros(n, dtype=torch.float64).index_add(0, row, w) + 1.0
+    dis = deg.pow(-0.5)
+    h = x @ kernel
+    out = torch.zeros(n, h.shape[1], dtype=torch.float64).index_add(0, row, (dis[row] * w * dis[col])[:, None] * h[col])
+    return out + h / deg[:, None] + bias
+
+
+def _batch_graph(seed, graphs=40, f=24):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sizes = rng.integers(5, 30, graphs)
+    gid = np.repeat(np.arange(graphs), sizes).astype(np.int32)
+    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    edges = []
+    for g, (s, c) in enumerate(zip(starts, sizes)):
+        for _ in range(2 * c):
+            a, b = rng.integers(s, s + c, 2)
+            edges += [(a, b), (b, a)]
+    ei = np.asarray(edges, dtype=np.int32).T.copy()
+    x = rng.standard_normal((gid.size, f)).astype(np.float32)
+    w = rng.uniform(0.5, 1.5, ei.shape[1]).astype(np.float32)
+    return x, ei, w, gid
+
+
+def test_sag_pool_gradients_match_float64(tfg):
+    """dx and the score gradient through tanh and GCN(1) (kernel, bias) against float64 torch autograd on the CPU.
+    d score = sum_f g x in fp32: the bound is 1e-5 relative to the float64 sum of |terms| of each gradient entry (fp32
+    cancellation can make the 1e-5 * |value| band unreachable for sums that nearly cancel)."""
+    dev = torch.device("cuda")
+    x_np, ei_np, w_np, gid_np = _batch_graph(1)
+    n, f = x_np.shape
+    rng = np.random.Generator(np.random.PCG64(2))
+    kern = (rng.uniform(-1, 1, (f, 1)) * 0.4).astype(np.float32)
+    bias = np.asarray([0.1], np.float32)
+    gcn = tfg.layers.GCN(1)
+    gcn._maybe_build([x_np])
+    gcn.set_weights(kernel=kern, bias=bias)
+    gcn.trainable(True)
+    x = torch.from_numpy(x_np).to(dev).requires_grad_(True)
+    ei, w, gid = (torch.from_numpy(a).to(dev) for a in (ei_np, w_np, gid_np))
+    px, pei, pw, pgi = tfg.nn.sag_pool(x, ei, w, gid, gcn, ratio=0.5, score_activation=torch.tanh)
+    G = torch.from_numpy(rng.standard_normal(tuple(px.shape)).astype(np.float32)).to(dev)
+    (px * G).sum().backward()
+    # the kept nodes, as the product ranked them (ranking is not differentiable; ties would make a float64 re-ranking
+    # legitimately different)
+    with torch.no_grad():
+        s32 = gcn([x.detach(), ei, w])
+    keep = tfg.nn.topk_pool(gid, s32, ratio=0.5).long().cpu()
+
+    x64 = torch.from_numpy(x_np).double().requires_grad_(True)
+    k64 = torch.from_numpy(kern).double().requires_grad_(True)
+    b64 = torch.from_numpy(bias).double().requires_grad_(True)
+    ei_c = torch.from_numpy(ei_np)
+    s64 = _gcn64(x64, ei_c, torch.from_numpy(w_np).double(), k64, b64, n)
+    p64 = (x64 * torch.tanh(s64))[keep]
+    assert_parity(px.detach().cpu().numpy(), p64.detach().numpy(), what="pooled x")
+    G64 = G.double().cpu()
+    (p64 * G64).sum().backward()
+    # |terms| bound: the same composition on absolute values
+    with torch.no_grad():
+        xa = x64.detach().abs()
+        sa = _gcn64(xa, ei_c, torch.from_numpy(w_np).double(), k64.detach().abs(), b64.detach().abs(), n)
+    xa2 = xa.clone().requires_grad_(True)
+    ka = k64.detach().abs().requires_grad_(True)
+    ba = b64.detach().abs().requires_grad_(True)
+    sa = _gcn64(xa2, ei_c, torch.from_numpy(w_np).double(), ka, ba, n)
+    ((xa2 * (1.0 + sa.abs()))[keep] * G64.abs()).sum().backward()
+    for name, got, ref, scale in (("dx", x.grad, x64.grad, xa2.grad), ("dkernel", gcn.kernel.grad, k64.grad, ka.grad),
+                                  ("dbias", gcn.bias.grad, b64.grad, ba.grad)):
+        d = (got.detach().double().cpu() - ref).abs()
+        bound = 1e-5 * (scale + ref.abs()) + 1e-7
+        assert bool((d <= bound).all()), "{}: max excess {:.3e}".format(name, float((d - bound).max()))
+
+
+def test_score_gradient_and_sort_pool_gradient(tfg):
+    """A leaf score: d score = sum_f g[node_map] x exactly as float64 within 1e-5 of sum_f |g x|; SortPool's dx is a
+    plain scatter (bit-exact)."""
+    dev = torch.device("cuda")
+    x_np, ei_np, w_np, gid_np = _batch_graph(4, f=37)      # F % 4 != 0: the scalar tail path
+    n = x_np.shape[0]
+    rng = np.random.Generator(np.random.PCG64(6))
+    s_np = rng.standard_normal((n, 1)).astype(np.float32)
+    x = torch.from_numpy(x_np).to(dev).requires_grad_(True)
+    s = torch.from_numpy(s_np).to(dev).requires_grad_(True)
+    ei, gid = torch.from_numpy(ei_np).to(dev), torch.from_numpy(gid_np).to(dev)
+    px, _, _, _ = tfg.nn.sag_pool(x, ei, None, gid, lambda inp, training=None: s, k=7)
+    G = torch.from_numpy(rng.standard_normal(tuple(px.shape)).astype(np.float32)).to(dev)
+    (px * G).sum().backward()
+    keep = tfg.nn.topk_pool(gid, s.detach(), k=7).long().cpu()
+    x64 = torch.from_numpy(x_np).double().requires_grad_(True)
+    s64 = torch.from_numpy(s_np).double().requires_grad_(True)
+    ((x64 * s64)[keep] * G.double().cpu()).sum().backward()
+    assert np.array_equal(x.grad.cpu().numpy(), x64.grad.numpy().astype(np.float32))    # one product each
+    gx = torch.zeros(n, x_np.shape[1], dtype=torch.float64)
+    gx[keep] = G.double().cpu().abs()
+    bound = 1e-5 * (gx * x64.detach().abs()).sum(1, keepdim=True) + 1e-30
+    assert bool(((s.grad.double().cpu() - s64.grad).abs() <= bound).all())
+    assert float(s.grad.cpu()[torch.from_numpy(np.setdiff1d(np.arange(n), keep.numpy()))].abs().max()) == 0.0
+
+    x.grad = None
+    px, _, _, _ = tfg.nn.sort_pool(x, ei, None, gid, ratio=0.5, sort_index=3)
+    G = torch.from_numpy(rng.standard_normal(tuple(px.shape)).astype(np.float32)).to(dev)
+    (px * G).sum().backward()
+    keep = tfg.nn.topk_pool(gid, x.detach()[:, 3], ratio=0.5).long()
+    ref = torch.zeros_like(x)
+    ref[keep] = G
+    assert torch.equal(x.grad, ref)
+
+
+def test_pooled_edge_weight_is_differentiable(tfg):
+    dev = torch.device("cuda")
+    x_np, ei_np, w_np, gid_np = _batch_graph(7)
+    w = torch.from_numpy(w_np).to(dev).requires_grad_(True)
+    s = torch.from_numpy(np.linspace(-1, 1, x_np.shape[0]).astype(np.float32)).to(dev)
+    px, pei, pw, _ = tfg.nn.sag_pool(torch.from_numpy(x_np).to(dev), torch.from_numpy(ei_np).to(dev), w,
+                                     torch.from_numpy(gid_np).to(dev), lambda inp, training=None: s[:, None], ratio=0.5)
+    G = torch.rand_like(pw)
+    (pw * G).sum().backward()
+    keep_ids = torch.from_numpy(_np_induced(ei_np, tfg.nn.topk_pool(torch.from_numpy(gid_np).to(dev), s,
+                                                                     ratio=0.5).cpu().numpy(), x_np.shape[0])[1]).to(dev)
+    ref = torch.zeros_like(w)
+    ref[keep_ids] = G
+    assert torch.equal(w.grad, ref) and torch.equal(pw.detach(), w.detach()[keep_ids])
+
+
+def test_determinism(tfg):
+    """Two runs: bit-identical pooled graphs and gradients."""
+    dev = torch.device("cuda")
+    x_np, ei_np, w_np, gid_np = _batch_graph(8, graphs=60, f=64)
+
+    def run():
+        gcn = tfg.layers.GCN(1, seed=3)
+        gcn.trainable(True)
+        x = torch.from_numpy(x_np).to(dev).requires_grad_(True)
+        out = tfg.nn.sag_pool(x, torch.from_numpy(ei_np).to(dev), torch.from_numpy(w_np).to(dev),
+                              torch.from_numpy(gid_np).to(dev), gcn, ratio=0.5, score_activation=torch.tanh)
+        (out[0] * torch.arange(out[0].numel(), device=dev, dtype=torch.float32).reshape(out[0].shape).sin()).sum().backward()
+        return [t.detach().clone() for t in out] + [x.grad.clone(), gcn.kernel.grad.clone(), gcn.bias.grad.clone()]
+
+    a, b = run(), run()
+    for u, v in zip(a, b):
+        assert torch.equal(u, v)
+
+
+# ---- errors ------------------------------------------------------------------------------------------------------------
+def test_invalid_node_index_raises(tfg):
+    from tf_geometric_amd._lib import TfgxError
+    dev = torch.device("cuda")
+    g = pc.batch()
+    ei = torch.from_numpy(g["ei"]).to(dev)
+    n = g["n"]
+    for bad in ([0, 1, 1], [0, n], [-1, 2]):
+        with pytest.raises(TfgxError, match="node_index"):
+            tfg.utils.sample_new_graph_by_node_index(ei, torch.tensor(bad, dtype=torch.int32, device=dev),
+                                                     x=torch.from_numpy(g["x"]).to(dev))
+    with pytest.raises(TfgxError):      # an edge endpoint outside the node range
+        tfg.utils.sample_new_graph_by_node_index(ei, [0, 1], x=np.zeros((3, 2), np.float32))
+    res = tfg.utils.sample_new_graph_by_node_index(g["ei"], [2, 0, 5], x=g["x"])     # the stream is still usable
+    assert res[0].shape == (3, g["f"])
+
+
+def test_refused_inside_graph_capture(tfg):
+    dev = torch.device("cuda")
+    g = pc.batch()
+    x, ei, gid = (torch.from_numpy(g[k]).to(dev) for k in ("x", "ei", "gid"))
+    s = torch.from_numpy(g["score"]).to(dev)
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with pytest.raises(RuntimeError, match="capture"):
+            with torch.cuda.graph(graph, stream=side):
+                tfg.nn.sag_pool(x, ei, None, gid, lambda inp, training=None: s, k=2)
+    torch.cuda.synchronize()
+
+
+# ---- the hierarchical model --------------------------------------------------------------------------------------------
+def test_sag_pool_h_trains(tfg):
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import demo_sag_pool_h as demo
+    data = demo.make_dataset(num_graphs=256, seed=0)
+    model = demo.SAGPoolHModel(data.num_features, data.num_classes, seed=0)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-2)
+    batch = demo.make_batch(data, list(range(128)))
+    losses = []
+    for _ in range(15):
+        loss = demo.train_step(model, opt, batch)
+        losses.append(loss)
+    assert all(np.isfinite(losses))
+    assert np.mean(losses[-3:]) < np.mean(losses[:3]) - 0.03, losses

@@ -209,6 +209,14 @@ SIGNATURES = {
     "tfgx_gemm_bias_act_cols_f32": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I32, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "tfgx_l2_normalize_rows_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _P]),
     "tfgx_sample_neighbors": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I32, _I32, ctypes.c_uint64, _P, _P, _P]),
+    "tfgx_induced_subgraph_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I32]),
+    "tfgx_induced_subgraph_count": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, ctypes.POINTER(ctypes.c_int64), _P,
+                                                   _SZ, _P]),
+    "tfgx_induced_subgraph_emit": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                  _P, _SZ, _P]),
+    "tfgx_gather_i32": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
+    "tfgx_gather_scale_rows_f32": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _P, _I64, _P]),
+    "tfgx_gather_scale_rows_backward_f32": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "tfgx_split_rows_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P]),
     "tfgx_split_rows_verify_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_uint64, _P, _P]),
     "tfgx_gather_rows_f32": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _I64, _P]),

@@ -971,3 +971,89 @@ def apply_activation(h, act, post):
     if act == L.ACT_RELU:
         h = torch.relu(h)
     return post(h) if post is not None else h
+
+
+class _GatherScale(torch.autograd.Function):
+    """out[i, :] = x[idx[i], :] * s[idx[i]] (SAGPool: (x * score)[kept]; s = None: SortPool's plain gather).
+    Forward = tfgx_gather_scale_rows_f32; backward = tfgx_gather_scale_rows_backward_f32, one launch over every parent row
+    through node_map (dropped rows get 0): dx = g[node_map] * s, ds = sum_f g[node_map] * x (fixed-order wave sum)."""
+
+    @staticmethod
+    def forward(ctx, x, s, idx, node_map):
+        lib = L.require_gpu()
+        x2, ldx = L.row_major_2d(x)
+        M, F = int(idx.shape[0]), int(x2.shape[1])
+        out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
+        L.check(lib.tfgx_gather_scale_rows_f32(L.ptr(x2), ldx, L.ptr(idx), L.ptr(s), M, F, L.ptr(out), max(F, 1),
+                                               L.stream_ptr()), "tfgx_gather_scale_rows_f32")
+        ctx.save_for_backward(x2, s, node_map)
+        ctx.has_s = s is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.require_gpu()
+        x2, s, node_map = ctx.saved_tensors
+        need_x = ctx.needs_input_grad[0]
+        need_s = ctx.has_s and ctx.needs_input_grad[1]
+        n, F = int(x2.shape[0]), int(x2.shape[1])
+        g2, ldg = L.row_major_2d(g.to(torch.float32))
+        dx = torch.empty((n, F), dtype=torch.float32, device=x2.device) if need_x else None
+        ds = torch.empty(n, dtype=torch.float32, device=x2.device) if need_s else None
+        ldx = x2.stride(0) if n > 1 else max(F, 1)
+        L.check(lib.tfgx_gather_scale_rows_backward_f32(L.ptr(g2), ldg, L.ptr(node_map), n, L.ptr(x2), ldx, L.ptr(s), F,
+                                                        L.ptr(dx), max(F, 1), L.ptr(ds), L.stream_ptr()),
+                "tfgx_gather_scale_rows_backward_f32")
+        return dx, ds, None, None
+
+
+def gather_scale(x, idx, node_map, s=None):
+    """(x * s[:, None])[idx] with s = a per-node multiplier ([n] or [n, 1]) or None; node_map[v] = position of v in idx
+    or -1 (tfgx_induced_subgraph_count).  Differentiable wrt x and s."""
+    n = int(x.shape[0])
+    if s is not None:
+        s = L.as_f32(s, x.device)
+        if s.numel() != n:
+            raise ValueError("the node score must hold one value per node ([{0}] or [{0}, 1]), got shape {1}".format(
+                n, tuple(s.shape)))
+        s = s.reshape(-1)
+        if not s.is_contiguous():
+            s = s.contiguous()
+    return _GatherScale.apply(x, s, L.as_i32(idx, x.device), node_map)
+
+
+def gather_edge_values(w, edge_id):
+    """w[edge_id] for a 1-D float32 tensor (tfgx_permute_rows_f32 with width 1)."""
+    lib = L.require_gpu()
+    w = w.contiguous()
+    out = torch.empty(int(edge_id.shape[0]), dtype=torch.float32, device=w.device)
+    if int(edge_id.shape[0]):
+        L.check(lib.tfgx_permute_rows_f32(L.ptr(w), L.ptr(edge_id), int(edge_id.shape[0]), 1, L.ptr(out), L.stream_ptr()),
+                "tfgx_permute_rows_f32")
+    return out
+
+
+class _GatherEdges(torch.autograd.Function):
+    """w[edge_id] for a tracked 1-D edge attribute; edge ids are unique, so the backward is a plain scatter into zeros
+    (tfgx_scatter_add_rows_f32 on a zeroed buffer: no conflicts, deterministic)."""
+
+    @staticmethod
+    def forward(ctx, w, edge_id):
+        ctx.save_for_backward(edge_id)
+        ctx.E = int(w.shape[0])
+        return gather_edge_values(w, edge_id)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.require_gpu()
+        (edge_id,) = ctx.saved_tensors
+        dw = torch.zeros(ctx.E, dtype=torch.float32, device=g.device)
+        gc = g.to(torch.float32).contiguous()
+        if int(edge_id.shape[0]):
+            L.check(lib.tfgx_scatter_add_rows_f32(L.ptr(dw), 1, L.ptr(edge_id), int(edge_id.shape[0]), 1, L.ptr(gc), 1,
+                                                  L.stream_ptr()), "tfgx_scatter_add_rows_f32")
+        return dw, None
+
+
+def gather_edges(w, edge_id):
+    return _GatherEdges.apply(L.as_f32(w).reshape(-1), edge_id)

@@ -1,2 +1,3 @@
 # coding=utf-8
 from .readout import CommonPool, MeanPool, SumPool, MaxPool, MinPool
+from .sag_pool import SAGPool, SortPool

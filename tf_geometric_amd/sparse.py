@@ -12,7 +12,8 @@ from .plan import CsrPlan, segment_reduce
 
 class SparseMatrix(object):
     def __init__(self, index, value=None, shape=None):
-        self.index = L.as_i32(index)
+        self._attached_plan = getattr(index, "_tfgx_plan", None)    # a producer that already knows the CSR (the sampler,
+        self.index = L.as_i32(index)                                # a pooling layer): CsrPlan.from_cache's rule
         if self.index.numel() == 0:
             self.index = self.index.reshape(2, 0)
         E = int(self.index.shape[1])
@@ -33,7 +34,9 @@ class SparseMatrix(object):
     @property
     def plan(self):
         if self._plan is None:
-            self._plan = CsrPlan.build(self.index, self._shape[0], self._shape[1])
+            attached = self._attached_plan
+            plan = attached.padded_to(self._shape[0], self._shape[1]) if attached is not None else None
+            self._plan = plan if plan is not None else CsrPlan.build(self.index, self._shape[0], self._shape[1])
         return self._plan
 
     @property

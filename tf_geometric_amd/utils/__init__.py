@@ -1,9 +1,11 @@
 # coding=utf-8
-"""The one piece of tf_geometric.utils the hot path touches: add_self_loop_edge (GAT prologue)."""
+"""The pieces of tf_geometric.utils around the hot path: add_self_loop_edge (GAT prologue), edge preprocessing, the
+neighbour sampler, and the node-induced subgraph of the pooling layers (subgraph.py)."""
 import numpy as np
 import torch
 
 from .. import _lib as L
+from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
 
 
 def add_self_loop_edge(edge_index, num_nodes, edge_weight=None, fill_weight=1.0):
