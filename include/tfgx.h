@@ -505,14 +505,18 @@ typedef struct tfgx_gat_backward_args {
        floats (tfgx_gat_pack_dst_heads_f32 writes it behind dO in the packed table).  With it the pass issues, per edge and
        lane, the dO load and B / 4 16-byte loads of that block — three line requests where q / stats_ml / dsum as separate
        pointers cost five (the L2s serve ~145 G requests/s: the pass went 3.9 -> 2.9 ms at Reddit shape).  q / stats_ml /
-       dsum stay mandatory: the one-lane kernels of odd head geometries read them. */
+       dsum stay mandatory: the one-lane kernels of odd head geometries read them.  Without head_pack the source pass reads
+       q / stats_ml / dsum (dense or interleaved) and gives the same bits as the head-pack route for the same inputs (same
+       dsum included): both divide 1 / (l + 1e-8) correctly rounded. */
     const float* head_pack;
     int64_t ld_head_pack;
 } tfgx_gat_backward_args;
 
 /* Prepares both backward passes in ONE sweep over the destination rows: dsum[r, h] = <dO[r, h, :], O[r, h, :]> (dense
    [n_dst, H]) and the packed table pack[r] = [ dO (H*dv) | Q (H*d) | (m, l) (2H) | D (H) ] with row stride ld_pack
-   (>= H*dv + H*d + 3H; a multiple of 32 floats keeps rows on whole 128-byte lines) that the source pass gathers. */
+   (>= H*dv + H*d + 3H; a multiple of 32 floats keeps rows on whole 128-byte lines) that the source pass gathers.
+   D is summed in dv-sequential fma order (as tfgx_gat_pack_dst_heads_f32 sums it) except on the 16-byte path (dv % 4 == 0,
+   dv / 4 a power of two, aligned rows), which adds the per-lane partials of a head in a butterfly: other bits. */
 int tfgx_gat_pack_dst_f32(const float* grad_out, int64_t ld_grad_out, const float* out, int64_t ldo, const float* q,
                           int64_t ldq, const float* stats_ml /* [n_dst, 2H] */, int64_t n_dst, int32_t H, int32_t d,
                           int32_t dv, float* pack, int64_t ld_pack, float* dsum /* [n_dst, H] */, tfgx_stream_t stream);

@@ -21,7 +21,8 @@ spot (margins: arguments `*_margin`, 20-100 x the float32 forward error) and ZER
 (GAT's Q / K projections) the INPUT rows whose pre-activations sit on the kink are redrawn first (`redraw_kink_rows`).
 Both are properties of the float64 reference alone: nothing of the product's output is consulted.
 
-Used by tests/test_gpu_fullsize.py only (the small-shape gradient tests keep their own CPU float64 references).
+Used by tests/test_gpu_fullsize.py; gat_attention_f64 at the end is the small-shape CPU reference of the attention
+gradient tests (tests/test_gpu_backward.py, tests/test_gpu_gat_backward_abi.py).
 """
 import math
 
@@ -258,3 +259,26 @@ def _gat(x32, ei, wq, bq, wk, bk, wv, bias, num_heads, G, x_grad, dtype, kink_ma
     grads = {"x": x.grad, "query_kernel": Wq.grad, "query_bias": Bq.grad, "key_kernel": Wk.grad, "key_bias": Bk.grad,
              "kernel": Wv.grad, "bias": gpre.sum(0)}
     return out, grads, G_eff.float()
+
+
+def gat_attention_f64(Q, K, V, row_ptr, col, heads, keep=None, rate=0.0):
+    """The fused attention (nn/conv/gat.py:73-89) over a CSR plan, differentiable: Q [n_dst, H*d], K [n_src, H*d],
+    V [n_src, H*dv] float64 leaves; row_ptr / col the plan's numpy arrays.  Edges in CSR order, then the self-loop (r, r)
+    of every destination r < n_dst at positions E .. E+n_dst-1 (gat.py:43); keep [E + n_dst, H] = the host restatement of
+    the attention-dropout mask (gat.py:85), applied as keep / (1 - rate).  Small graphs: plain index_add, no chunking."""
+    n = int(row_ptr.shape[0]) - 1
+    ar = torch.arange(n, dtype=torch.int64)
+    row = torch.cat([torch.repeat_interleave(ar, torch.from_numpy(row_ptr[1:] - row_ptr[:-1]).long()), ar])
+    col = torch.cat([torch.from_numpy(col).long(), ar])
+    d, dv = Q.shape[1] // heads, V.shape[1] // heads
+    outs = []
+    for h in range(heads):
+        s = (Q[row, h * d:(h + 1) * d] * K[col, h * d:(h + 1) * d]).sum(-1) / math.sqrt(d)
+        m = torch.full((n,), -1e30, dtype=torch.float64).scatter_reduce(0, row, s, "amax")
+        p = torch.exp(s - m[row].detach())
+        den = torch.zeros(n, dtype=torch.float64).index_add(0, row, p) + 1e-8
+        a = p / den[row]
+        if keep is not None:
+            a = a * torch.as_tensor(keep[:, h], dtype=torch.float64) / (1.0 - rate)
+        outs.append(torch.zeros(n, dv, dtype=torch.float64).index_add(0, row, a[:, None] * V[col, h * dv:(h + 1) * dv]))
+    return torch.cat(outs, 1)

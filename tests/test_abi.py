@@ -93,6 +93,24 @@ def test_argument_validation_without_gpu():
     g = _lib.GatArgs()
     g.H, g.d, g.dv, g.n_dst, g.scale, g.drop_rate = 2, 4, 4, 3, 2.0, 1.5
     assert lib.tfgx_gat_fused_f32(ctypes.byref(g), None) == 1
+    # GAT backward: bad head geometry / scale, and packed destination tables whose rows cannot hold what goes in them
+    gb = _lib.GatBackwardArgs()
+    gb.d, gb.dv, gb.n_dst, gb.n_src = 4, 8, 3, 3
+    for fn in (lib.tfgx_gat_backward_dst_f32, lib.tfgx_gat_backward_src_f32):
+        gb.H, gb.scale = 0, 2.0
+        assert fn(ctypes.byref(gb), None) == 1 and b"bad H / d / dv / scale" in lib.tfgx_last_error()
+        gb.H, gb.scale = 2, 0.0
+        assert fn(ctypes.byref(gb), None) == 1 and b"bad H / d / dv / scale" in lib.tfgx_last_error()
+    H, d, dv = 2, 4, 8                                     # W = 16, A = 8: [dO | Q | (m, l) | D] needs 30 floats a row
+    assert lib.tfgx_gat_pack_dst_f32(None, 16, None, 16, None, 8, None, 5, H, d, dv, None, 29, None, None) == 1
+    assert b"leading dimension too small" in lib.tfgx_last_error()
+    assert lib.tfgx_gat_pack_dst_f32(None, 16, None, 16, None, 8, None, 5, H, d, dv, None, 30, None, None) == 1
+    assert b"null pointer" in lib.tfgx_last_error()                                   # (30 is enough: the next check)
+    # head blocks: roundup4(16) + 2 * roundup4(4 + 3) = 32 floats a row
+    assert lib.tfgx_gat_pack_dst_heads_f32(None, 16, None, 16, None, 8, None, 5, H, d, dv, None, 31, None, None) == 1
+    assert b"ld_pack >= roundup4(H * dv) + H * roundup4(d + 3)" in lib.tfgx_last_error()
+    assert lib.tfgx_gat_pack_dst_heads_f32(None, 16, None, 16, None, 8, None, 5, H, d, dv, None, 32, None, None) == 1
+    assert b"null pointer" in lib.tfgx_last_error()
     assert lib.tfgx_dropout_keep(7, 3, 0.0) == 1                                      # rate 0 keeps everything
     kept = sum(lib.tfgx_dropout_keep(0x1234567890, i, 0.25) for i in range(4000))
     assert 2850 < kept < 3150                                                         # ~75 %

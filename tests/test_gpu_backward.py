@@ -212,21 +212,9 @@ def test_gat_attention_dropout_forward_and_grads(tfg, oracle, heads, att, units,
     out = AG.gat_attention(plan, t["Q"], t["K"], t["V"], heads, drop_rate=rate, drop_seed=seed)
     out.backward(torch.tensor(gout, device="cuda"))
     # float64 reference in CSR order, self-loops appended (positions E .. E+n-1)
-    rp = plan.row_ptr.cpu().numpy()
-    ar = np.arange(n, dtype=np.int64)
-    row = torch.from_numpy(np.concatenate([np.repeat(ar, np.diff(rp)), ar]))
-    col = torch.from_numpy(np.concatenate([plan.col.cpu().numpy().astype(np.int64), ar]))
+    from f64_layers import gat_attention_f64
     r = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in dict(Q=Q, K=K, V=V).items()}
-    d, dv = att // heads, units // heads
-    outs = []
-    for h in range(heads):
-        s = (r["Q"][row, h * d:(h + 1) * d] * r["K"][col, h * d:(h + 1) * d]).sum(-1) / np.sqrt(d)
-        m = torch.full((n,), -1e30, dtype=torch.float64).scatter_reduce(0, row, s, "amax")
-        p = torch.exp(s - m[row].detach())
-        den = torch.zeros(n, dtype=torch.float64).index_add(0, row, p) + 1e-8
-        a = p / den[row] * torch.from_numpy(keep[:, h].astype(np.float64)) / (1.0 - rate)
-        outs.append(torch.zeros(n, dv, dtype=torch.float64).index_add(0, row, a[:, None] * r["V"][col, h * dv:(h + 1) * dv]))
-    ref = torch.cat(outs, 1)
+    ref = gat_attention_f64(r["Q"], r["K"], r["V"], plan.row_ptr.cpu().numpy(), plan.col.cpu().numpy(), heads, keep=keep, rate=rate)
     ref.backward(torch.tensor(gout, dtype=torch.float64))
     assert_parity(out.detach().cpu().numpy(), ref.detach().numpy(), tol=2e-5, what="dropout forward")
     for k in ("Q", "K", "V"):

@@ -1047,6 +1047,15 @@ __global__ __launch_bounds__(kBlock) void gat_query_grad_d1_kernel(const float* 
     }
 }
 
+// keep * <dO, V> - D of the fast kernels with the product rounded on its own.  Left to contraction, the head-block source pass
+// pairs the product with alpha's in one packed multiply while the other source-pass instantiations fused it into an fma:
+// under attention dropout (keep != 1) the layouts of tfgx_gat_backward_args then disagreed in the last bits of dK.
+__device__ __forceinline__ float keep_da_minus_d(float keep, float da, float dd)
+{
+#pragma clang fp contract(off)
+    return keep * da - dd;
+}
+
 // POW2: a.inv_scale is the exact inverse of a power-of-two scale (instantiated for d = 1, 4, 16, where sqrt(d) is one)
 // HP (src pass only): the per-head scalars of the gathered destination come from a.hp (head blocks, see above)
 #ifndef TFGX_GAT_BWD_SRC_WAVES
@@ -1148,12 +1157,13 @@ __global__ __launch_bounds__(kBlock, (SRC && HP && D <= 4) ? TFGX_GAT_BWD_SRC_WA
         };
         auto edge_finish = [&](const EdgeIn& in, float sc, float da, float keep, auto pow2) {
             const float m = SRC ? in.m : m_r;
-            // 1 / (l + 1e-8): the destination pass divides once per row; per EDGE (source pass) the correctly rounded division
-            // is ten instructions of a walk bound by vector-ALU issue — v_rcp_f32 (1 ulp) there
-            const float linv = SRC ? (HP ? in.l : __builtin_amdgcn_rcpf(in.l + 1e-8f)) : linv_r;
+            // 1 / (l + 1e-8), correctly rounded on every route: the destination pass divides once per row, the head-block source
+            // pass reads the quotient gat_pack_dst_heads_kernel formed; the source pass over separate q / stats_ml / dsum (never
+            // the package's route) divides per edge, so that it gives the head-block route's bits for the same inputs
+            const float linv = SRC ? (HP ? in.l : 1.0f / (in.l + 1e-8f)) : linv_r;
             const float dd = SRC ? in.dd : d_r;
             const float alpha = expf(sc - m) * linv;
-            float ds = alpha * (keep * da - dd);
+            float ds = alpha * keep_da_minus_d(keep, da, dd);
             if constexpr (decltype(pow2)::value) ds = ds * a.inv_scale;
             else ds = ds / a.scale;
 #pragma unroll
