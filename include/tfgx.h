@@ -11,7 +11,8 @@
  *   - nothing is allocated here: outputs and workspaces are caller buffers;
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), except
  *     tfgx_build_csr_by_dst, tfgx_segment_topk and tfgx_induced_subgraph_count, which synchronise once to report
- *     bad indices (the last also to return its output size);
+ *     bad indices (the last also to return its output size), and tfgx_plan_row_order / tfgx_plan_hub_lists_count,
+ *     which synchronise once to read back a maximum / their output sizes;
  *   - return value: 0 = ok, otherwise a TFGX_ERR_* code; text via tfgx_last_error();
  *   - results are deterministic (no floating-point atomics anywhere);
  *   - index convention of the reference: edge_index[0] = row = DESTINATION (aggregating node),
@@ -72,6 +73,60 @@ int tfgx_permute_rows_f32(const float* src, const int32_t* perm, int64_t E, int6
                           tfgx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-plan structures of the fast routes, built on the device from a plan's row_ptr / col (no sort where a stable
+ * partition suffices).  Each is built once per plan and kept by the host; every output is int32.
+ *
+ * Policies (host functions, no GPU needed):
+ *   tfgx_hub_policy: (threshold, chunk) of the hub lists for a plan of E edges over n_dst rows — the smallest power of
+ *     two threshold in [128, 2048] that is at least 4x the mean in-degree, chunk = max(128, threshold / 2).
+ *   tfgx_gat_source_block_count: how many source blocks the chained tfgx_gat_fused_f32 launches should run in (1 = one
+ *     pass): min(round_half_even(n_src * (A + W) * 4 / block_bytes), trunc(E / n_dst / min_edges), 16), and 1 when that
+ *     is below 2 or n_dst == 0 or E == 0.  block_bytes 0 = 6 MB, min_edges 0 = 32.  Returns 0 on a negative argument.
+ *
+ * Walk order (tfgx_reduce_args.row_order, tfgx_gat_args.row_order, tfgx_gat_backward_args.row_order):
+ *   the rows sorted by descending in-degree, equal degrees in ascending row id, written to order[n_dst] ONLY when the
+ *   plan is skewed — longest row > 8 * max(E / n_dst, 1) edges (*skewed = 1, host); otherwise *skewed = 0 and order is
+ *   not touched.  SYNCHRONISES ONCE (the longest row is read back for the test).  row_ptr must be non-decreasing.
+ *
+ * Hub lists (tfgx_hub_lists; the hub_* members of tfgx_reduce_args / tfgx_gat_args), a count / emit pair sharing one
+ * workspace of tfgx_plan_hub_lists_workspace_bytes(n_rows) bytes.  Span r = [row_begin[r * rp_stride],
+ * row_end[r * rp_stride]) for r < n_rows (plain CSR: row_begin = row_ptr, row_end = row_ptr + 1, rp_stride = 1); spans
+ * longer than `threshold` are hub rows, cut into chunks of `chunk` positions:
+ *   _count : SYNCHRONISES ONCE to return the number of hub rows and of chunks (host).
+ *   _emit  : (same arguments and workspace, the two counts from _count) writes rows[n_hub_rows] (ascending),
+ *            chunk_ptr[n_hub_rows + 1], chunk_begin / chunk_end / chunk_row[n_chunks].  Nothing is written when
+ *            n_hub_rows == 0.  Asynchronous.
+ *
+ * hub_order_slot (tfgx_reduce_args.hub_order_slot): slot[i] = position of order[i] in the ascending hub_rows (the first
+ *   position whose id is >= order[i]) for i < n_hub — with a walk order and hub lists of the same plan, order[0 .. n_hub)
+ *   are the hub rows.  Asynchronous.
+ *
+ * Source blocks (the chained tfgx_gat_fused_f32 launches: row_begin = rpk + b, row_end = rpk + b + 1, rp_stride = KB):
+ *   block b = sources [b * blk, (b + 1) * blk), blk = max(ceil(n_src / KB), 1).  rpk[r * KB + b] = row_ptr[r] + (row r's
+ *   edges in blocks < b), rpk[n_dst * KB] = E; col_k[E] = col with every row's edges stably partitioned by block (row r's
+ *   block-b edges at [rpk[r * KB + b], rpk[r * KB + b + 1]), in their CSR order).  1 <= KB <= 64 (one lane per block);
+ *   KB = 1 is a copy.  No workspace, asynchronous; any row length (one wave per row).
+ * ------------------------------------------------------------------------------------------- */
+int tfgx_hub_policy(int64_t E, int64_t n_dst, int32_t* threshold /* host */, int32_t* chunk /* host */);
+int32_t tfgx_gat_source_block_count(int64_t n_dst, int64_t n_src, int64_t E, int64_t A, int64_t W, int64_t block_bytes,
+                                    int64_t min_edges);
+size_t tfgx_plan_row_order_workspace_bytes(int64_t n_dst);
+int tfgx_plan_row_order(const int32_t* row_ptr, int64_t n_dst, int64_t E, int32_t* order /* [n_dst] */,
+                        int32_t* skewed /* host */, void* workspace, size_t workspace_bytes, tfgx_stream_t stream);
+size_t tfgx_plan_hub_lists_workspace_bytes(int64_t n_rows);
+int tfgx_plan_hub_lists_count(const int32_t* row_begin, const int32_t* row_end, int64_t rp_stride, int64_t n_rows,
+                              int32_t threshold, int32_t chunk, int64_t* n_hub_rows /* host */,
+                              int64_t* n_chunks /* host */, void* workspace, size_t workspace_bytes, tfgx_stream_t stream);
+int tfgx_plan_hub_lists_emit(const int32_t* row_begin, const int32_t* row_end, int64_t rp_stride, int64_t n_rows,
+                             int32_t threshold, int32_t chunk, int64_t n_hub_rows, int64_t n_chunks, int32_t* rows,
+                             int32_t* chunk_ptr, int32_t* chunk_begin, int32_t* chunk_end, int32_t* chunk_row,
+                             void* workspace, size_t workspace_bytes, tfgx_stream_t stream);
+int tfgx_plan_hub_order_slot(const int32_t* hub_rows, int64_t n_hub, const int32_t* order, int32_t* slot,
+                             tfgx_stream_t stream);
+int tfgx_plan_source_blocks(const int32_t* row_ptr, const int32_t* col, int64_t n_dst, int64_t n_src, int64_t E, int32_t KB,
+                            int32_t* rpk /* [n_dst * KB + 1] */, int32_t* col_k /* [E] */, tfgx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge preprocessing right before the path: merge_duplicated_edge
  * (tf_geometric/utils/graph_utils.py:67-125) = tf.unique over the hash n*row+col.  Outputs the unique edges in
  * FIRST-OCCURRENCE order (tf.unique's order) and unique_index[E] (edge -> unique edge), with which edge
@@ -118,7 +173,8 @@ typedef struct tfgx_reduce_args {
     const float* add_x;       /* [n_dst, ld_add] or NULL: sum_updater's "x +" */
     int64_t ld_add;
     const int32_t* mean_count;/* [n_dst] or NULL: divisor for TFGX_MEAN (NULL: row_end-row_begin); <1 -> 1 */
-    /* hub rows (only read when hub_threshold > 0 and n_hub_rows > 0); built once per plan by the host */
+    /* hub rows (only read when hub_threshold > 0 and n_hub_rows > 0); built once per plan by tfgx_plan_hub_lists_count /
+       _emit with the thresholds of tfgx_hub_policy */
     const int32_t* hub_rows;        /* [n_hub_rows] destination ids with in-degree > hub_threshold, ascending */
     const int32_t* hub_chunk_ptr;   /* [n_hub_rows+1] chunk range of each hub row */
     const int32_t* hub_chunk_begin; /* [n_hub_chunks] CSR positions: chunk c covers [begin[c], end[c]) */
@@ -140,8 +196,8 @@ typedef struct tfgx_reduce_args {
     const float* edge_tail;
     int64_t ld_edge_tail;
     /* optional walk order: lane group i of the launch reduces destination row row_order[i] (NULL: i) — the plan's rows
-       sorted by length on skewed graphs, so that the rows sharing a wave are of similar length; a permutation of
-       [0, n_dst), results do not depend on it */
+       sorted by length on skewed graphs (tfgx_plan_row_order), so that the rows sharing a wave are of similar length; a
+       permutation of [0, n_dst), results do not depend on it */
     const int32_t* row_order;
     /* optional, TFGX_MAX only (the TRAINING forward of max aggregation): per output element one uint32 =
        (number of edges attaining the row maximum, saturating at 65535) << 16 | (CSR position of the FIRST such edge
@@ -160,7 +216,8 @@ typedef struct tfgx_reduce_args {
     const int32_t* track_row_begin;
     /* optional, read by tfgx_aggregate_gemm_f32 only, with row_order and hub lists: hub_order_slot[i] = index into hub_rows of
        destination row row_order[i], for i < n_hub_rows (a walk order sorted by descending length puts the hub rows first).
-       Checked against hub_rows before use; NULL or a mismatch costs a binary search per hub row instead of one load. */
+       Checked against hub_rows before use; NULL or a mismatch costs a binary search per hub row instead of one load.
+       Built by tfgx_plan_hub_order_slot. */
     const int32_t* hub_order_slot;
     /* Wide rows (F >= 128 made of whole 128-byte lines; tfgx_segment_reduce_f32 only): 0 = the library's policy — column blocks
        of 64 columns on grid.y, every pass gathering one block of every source row (round 5: +7 ... +17 % at F = 128 ... 512 on
@@ -255,7 +312,7 @@ typedef struct tfgx_gat_args {
        tfgx_gat_merge_passes_f32. */
     float* state_acc;              /* [n_dst, H*dv] */
     float* state_ml;               /* [n_dst, 2*H]  */
-    /* hub rows (as in tfgx_reduce_args) + the destination of every chunk and two scratch arrays */
+    /* hub rows (as in tfgx_reduce_args: tfgx_plan_hub_lists_*) + the destination of every chunk and two scratch arrays */
     int32_t hub_threshold;
     int32_t reserved;
     const int32_t* hub_rows;
@@ -279,7 +336,7 @@ typedef struct tfgx_gat_args {
     uint64_t drop_seed;
     int64_t drop_self_base;
     /* optional walk order: lane group i of the launch processes destination row_order[i] (NULL: i).  On a power-law graph
-       the host passes the rows sorted by in-degree, so that the rows sharing a wave have similar lengths (13-16 % on the
+       the host passes the rows sorted by in-degree (tfgx_plan_row_order), so that the rows sharing a wave have similar lengths (13-16 % on the
        whole layer at R-MAT shapes); results do not depend on it.  Ignored by the part / chunk launches. */
     const int32_t* row_order;
     /* optional, with drop_rate > 0: the seed is read from this DEVICE location by the kernel instead of drop_seed — for
@@ -290,7 +347,7 @@ typedef struct tfgx_gat_args {
        state_acc / state_ml hold them, same indexing — instead of the empty state, and ends as usual: with state_acc set the
        updated raw state is written (it must not alias the state read), without it the row is finished (self-loop, normalise,
        bias, activation, stats_ml).  Chaining KB launches over the SOURCE BLOCKS of a plan whose rows are partitioned by
-       source range (row_begin / row_end / rp_stride = KB) makes every launch gather K / V rows of one block only: on a dense
+       source range (tfgx_plan_source_blocks; row_begin / row_end / rp_stride = KB, KB from tfgx_gat_source_block_count) makes every launch gather K / V rows of one block only: on a dense
        graph (Reddit shape: 489 in-edges per node, 67 MB of K | V rows) a block fits the L2 of every XCD and the layer's
        attention runs 1.5x faster.  Not combinable with drop_rate > 0 or the hub lists. */
     const float* state_in_acc;     /* [n_parts, H*dv] */
@@ -434,8 +491,8 @@ int tfgx_pool_mlp_max_wgrad_f32(const int32_t* row_ptr, const int32_t* col, int6
                                 int64_t lddw, float* db /* [Fp] or NULL */, void* workspace, size_t workspace_bytes,
                                 tfgx_stream_t stream);
 
-/* Chunk lists of the rows of a plan that are too long for one lane group ("hubs" of a power-law graph), as the host
-   builds them once per plan (the same lists tfgx_reduce_args / tfgx_gat_args carry for the forward): rows with more
+/* Chunk lists of the rows of a plan that are too long for one lane group ("hubs" of a power-law graph), as
+   tfgx_plan_hub_lists_count / _emit build them once per plan (the same lists tfgx_reduce_args / tfgx_gat_args carry for the forward): rows with more
    than `threshold` positions; hub row rows[i] owns chunks [chunk_ptr[i], chunk_ptr[i+1]); chunk c covers CSR positions
    [chunk_begin[c], chunk_end[c]) of row chunk_row[c].  The *_hub_f32 backward entry points below take them (NULL: every
    row is walked by one lane group), run the hub rows chunk-wise into a caller-lent scratch and add a row's chunk

@@ -3,6 +3,7 @@
 import os
 import subprocess
 import sys
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -11,7 +12,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libtfgx.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_misc.hip", "tfgx_backward.hip",
-           "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip"]
+           "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -49,6 +50,10 @@ def build(force=False, verbose=True):
     build_dist(force=force or bool(jobs), verbose=verbose)
     build_line_rate_probe(force=force, verbose=verbose)
     build_c_abi_demo(force=force or bool(jobs), verbose=verbose)
+    try:        # an example program: a failed compile must not fail the library build
+        build_c_abi_gat_demo(force=force or bool(jobs), verbose=verbose)
+    except (OSError, subprocess.CalledProcessError) as ex:
+        warnings.warn("tf_geometric_amd: building {} failed ({}); the library itself is built".format(GAT_DEMO_BIN, ex))
     build_tf_shim_mock(force=force or bool(jobs), verbose=verbose)
     return LIB_PATH
 
@@ -116,6 +121,24 @@ def build_c_abi_demo(force=False, verbose=True):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     return DEMO_BIN
+
+
+GAT_DEMO_SRC = os.path.join(_HERE, "..", "examples", "c_abi_gat_demo.cpp")
+GAT_DEMO_BIN = os.path.join(LIB_DIR, "c_abi_gat_demo")
+
+
+def build_c_abi_gat_demo(force=False, verbose=True):
+    """examples/c_abi_gat_demo.cpp: the fast GAT attention routes (source blocks / walk order + hub lists) from a host that
+    has only include/tfgx.h and libtfgx.so — run by tests/test_gpu_c_abi_gat.py on the GPU box."""
+    if not os.path.exists(GAT_DEMO_SRC):
+        return None
+    if force or _newer(GAT_DEMO_SRC, GAT_DEMO_BIN) or _newer(LIB_PATH, GAT_DEMO_BIN):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-I", os.path.join(_HERE, "..", "include"), GAT_DEMO_SRC,
+               "-L", LIB_DIR, "-ltfgx", "-Wl,-rpath,$ORIGIN", "-o", GAT_DEMO_BIN]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return GAT_DEMO_BIN
 
 
 SHIM_DIR = os.path.join(_HERE, "..", "integration", "tf_shim")

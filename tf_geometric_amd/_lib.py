@@ -227,6 +227,16 @@ SIGNATURES = {
     "tfgx_split_by_source_class": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _P]),
     "tfgx_aggregate_gemm_fits": (ctypes.c_int, [_I64, _I64]),
     "tfgx_aggregate_gemm_f32": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _P, _I64, _P, _I32, _P, _I64, _I64, _P]),
+    "tfgx_hub_policy": (ctypes.c_int, [_I64, _I64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "tfgx_gat_source_block_count": (ctypes.c_int32, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
+    "tfgx_plan_row_order_workspace_bytes": (_SZ, [_I64]),
+    "tfgx_plan_row_order": (ctypes.c_int, [_P, _I64, _I64, _P, ctypes.POINTER(ctypes.c_int32), _P, _SZ, _P]),
+    "tfgx_plan_hub_lists_workspace_bytes": (_SZ, [_I64]),
+    "tfgx_plan_hub_lists_count": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _I32, ctypes.POINTER(ctypes.c_int64),
+                                                 ctypes.POINTER(ctypes.c_int64), _P, _SZ, _P]),
+    "tfgx_plan_hub_lists_emit": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "tfgx_plan_hub_order_slot": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
+    "tfgx_plan_source_blocks": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }
 
 _lib = None

@@ -153,11 +153,13 @@ def source_block_count(plan, A, W):
     Reddit shape (233 k nodes, 489 in-edges each, A = 8, W = 64): 11 blocks; products shape (51 in-edges): 1."""
     if SOURCE_BLOCKS is not None:
         return max(int(SOURCE_BLOCKS), 1)
-    if plan.n_dst == 0 or plan.num_edges == 0:
-        return 1
-    table = plan.n_src * (int(A) + int(W)) * 4
-    kb = min(int(round(table / float(SOURCE_BLOCK_BYTES))), int(plan.num_edges / float(plan.n_dst) / SOURCE_BLOCK_MIN_EDGES), 16)
-    return kb if kb >= 2 else 1
+    # the policy lives in the library (tfgx_gat_source_block_count), so that C / TF hosts pick the same KB:
+    # min(round(table / SOURCE_BLOCK_BYTES), int(E / n_dst / SOURCE_BLOCK_MIN_EDGES), 16), 1 below 2
+    kb = L.load_library().tfgx_gat_source_block_count(plan.n_dst, plan.n_src, plan.num_edges, int(A), int(W),
+                                                       int(SOURCE_BLOCK_BYTES), int(SOURCE_BLOCK_MIN_EDGES))
+    if kb < 1:
+        L.check(1, "tfgx_gat_source_block_count")
+    return int(kb)
 
 
 def _gat_attention_source_blocks(plan, blocks, KB, Q, K, V, num_heads, add_self_loop, bias, act, stats_ml, scale_d, qsums=None):

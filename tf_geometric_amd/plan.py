@@ -118,29 +118,28 @@ class CsrPlan(object):
     def row_order(self):
         """Rows sorted by descending length (int32 [n_dst]) when the plan is skewed — longest row more than 8x the mean —
         else None.  Kernels that give every row a lane group walk the rows in this order so that the rows sharing a wave
-        have similar lengths (GAT layer on R-MAT graphs: 13-16 %); results do not depend on it.  Computed once per plan."""
+        have similar lengths (GAT layer on R-MAT graphs: 13-16 %); results do not depend on it.  Computed once per plan, on the
+        device (tfgx_plan_row_order)."""
         if getattr(self, "_row_order", None) is None:
             if torch.cuda.is_current_stream_capturing():
                 return None      # the skew test synchronises (deg.max().item()): never inside a hipGraph capture —
                                  # results do not depend on the order, and the next eager call computes and keeps it
             order = False
             if self.n_dst > 0 and self.num_edges > 0:
-                deg = self.in_degree()
-                if int(deg.max().item()) > 8 * max(self.num_edges / float(self.n_dst), 1.0):
-                    order = torch.argsort(deg, descending=True, stable=True).to(torch.int32).contiguous()
-            self._row_order = order
+                order = build_row_order(self.row_ptr, self.n_dst, self.num_edges)
+            self._row_order = False if order is None else order
         return None if self._row_order is False else self._row_order
 
     def hub_info(self):
         """Chunk lists for destinations with more than hub_threshold in-edges (power-law "hubs"), or None.
-        Small control-plane metadata, computed once per plan:
+        Small control-plane metadata, computed once per plan on the device (tfgx_plan_hub_lists_*):
         (hub_rows, chunk_ptr, chunk_begin, chunk_end, chunk_row)."""
         if self._hub is None:
             if torch.cuda.is_current_stream_capturing():
                 return None      # building the lists synchronises; long rows then run inline (same sums, slower)
             thr, chunk = hub_policy(self.num_edges, self.n_dst)
             self.hub_threshold = thr
-            self._hub = build_hub_lists(self.row_ptr[:-1], self.row_ptr[1:], thr, chunk) or False
+            self._hub = build_hub_lists_device(self.row_ptr[:-1], self.row_ptr[1:], 1, self.n_dst, thr, chunk) or False
         return self._hub or None
 
     def source_blocks(self, num_blocks):
@@ -148,23 +147,20 @@ class CsrPlan(object):
         [b * ceil(n_src / KB), (b + 1) * ...)): (rpk int32 [n_dst * KB + 1], col_k int32 [E]) — row r's edges
         from block b sit at positions [rpk[r * KB + b], rpk[r * KB + b + 1]) of col_k (a row's edges keep their order inside a block).  KB chained
         launches over the blocks (row_begin = rpk + b, row_end = rpk + b + 1, rp_stride = KB) each gather rows of one block
-        only (nn/conv/gat.py: dense graphs whose K | V table fits the L2 block by block).  Built once per (plan, KB) with
-        device sorts; E * 12 bytes while building, E * 4 + n_dst * KB * 4 kept."""
+        only (nn/conv/gat.py: dense graphs whose K | V table fits the L2 block by block).  Built once per (plan, KB) by
+        tfgx_plan_source_blocks (1 <= KB <= 64; no sort, no temporaries): E * 4 + n_dst * KB * 4 bytes kept."""
         KB = int(num_blocks)
         memo = self.__dict__.setdefault("_source_blocks", {})
         if KB not in memo:
             if torch.cuda.is_current_stream_capturing():
                 return None
+            lib = L.require_gpu()
             dev = self.col.device
-            blk = max(-(-self.n_src // KB), 1)
-            rows = torch.repeat_interleave(torch.arange(self.n_dst, device=dev, dtype=torch.int64), self.in_degree().long())
-            key = rows * KB + torch.div(self.col.long(), blk, rounding_mode="floor")
-            del rows
-            order = torch.argsort(key, stable=True)
-            rpk = torch.zeros(self.n_dst * KB + 1, dtype=torch.int32, device=dev)
-            rpk[1:] = torch.cumsum(torch.bincount(key, minlength=self.n_dst * KB), 0).to(torch.int32)
-            del key
-            memo[KB] = (rpk, self.col[order].contiguous())
+            rpk = torch.empty(self.n_dst * KB + 1, dtype=torch.int32, device=dev)
+            col_k = torch.empty(self.num_edges, dtype=torch.int32, device=dev)
+            L.check(lib.tfgx_plan_source_blocks(L.ptr(self.row_ptr), L.ptr(self.col), self.n_dst, self.n_src, self.num_edges,
+                                                KB, L.ptr(rpk), L.ptr(col_k), L.stream_ptr()), "tfgx_plan_source_blocks")
+            memo[KB] = (rpk, col_k)
         return memo[KB]
 
     def hub_order_slot(self):
@@ -175,14 +171,56 @@ class CsrPlan(object):
             slot = False
             if hub is not None and order is not None:
                 n_hub = int(hub[0].shape[0])
-                slot = torch.searchsorted(hub[0], order[:n_hub].contiguous()).to(torch.int32).contiguous()
+                slot = torch.empty(n_hub, dtype=torch.int32, device=order.device)
+                L.check(L.require_gpu().tfgx_plan_hub_order_slot(L.ptr(hub[0]), n_hub, L.ptr(order), L.ptr(slot),
+                                                                 L.stream_ptr()), "tfgx_plan_hub_order_slot")
             self._hub_order_slot = slot
         return None if self._hub_order_slot is False else self._hub_order_slot
 
 
+def build_row_order(row_ptr, n_dst, num_edges):
+    """tfgx_plan_row_order: int32 [n_dst] = the rows by descending in-degree (ties in ascending row id; what
+    torch.argsort(deg, descending=True, stable=True) gives) when the plan is skewed — longest row more than
+    8 * max(E / n_dst, 1) edges — else None.  Synchronises once (the longest row is read back)."""
+    lib = L.require_gpu()
+    dev = row_ptr.device
+    order = torch.empty(max(int(n_dst), 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(lib.tfgx_plan_row_order_workspace_bytes(n_dst), 1), dtype=torch.uint8, device=dev)
+    skewed = ctypes.c_int32(0)
+    L.check(lib.tfgx_plan_row_order(L.ptr(row_ptr), int(n_dst), int(num_edges), L.ptr(order), ctypes.byref(skewed), L.ptr(ws),
+                                    ws.numel(), L.stream_ptr()), "tfgx_plan_row_order")
+    return order[:int(n_dst)] if skewed.value else None
+
+
+def build_hub_lists_device(span_begin, span_end, rp_stride, n_rows, threshold, chunk):
+    """build_hub_lists(span_begin[::rp_stride][:n_rows], span_end[::rp_stride][:n_rows], threshold, chunk), bit for bit, by
+    tfgx_plan_hub_lists_count / _emit (span_begin / span_end: int32 device tensors with unit stride; the strided form
+    reads the spans in place).  Synchronises once (the two list sizes)."""
+    lib = L.require_gpu()
+    dev = span_begin.device
+    n_rows = int(n_rows)
+    if n_rows == 0:
+        return None
+    assert span_begin.dtype == torch.int32 and span_end.dtype == torch.int32
+    assert span_begin.stride(0) == 1 and span_end.stride(0) == 1
+    ws = torch.empty(max(lib.tfgx_plan_hub_lists_workspace_bytes(n_rows), 1), dtype=torch.uint8, device=dev)
+    spans = (L.ptr(span_begin), L.ptr(span_end), int(rp_stride), n_rows, int(threshold), int(chunk))
+    n_hub, n_chunks = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(lib.tfgx_plan_hub_lists_count(*spans, ctypes.byref(n_hub), ctypes.byref(n_chunks), L.ptr(ws), ws.numel(),
+                                          L.stream_ptr()), "tfgx_plan_hub_lists_count")
+    nh, nc = n_hub.value, n_chunks.value
+    if nh == 0:
+        return None
+    out = tuple(torch.empty(k, dtype=torch.int32, device=dev) for k in (nh, nh + 1, nc, nc, nc))
+    L.check(lib.tfgx_plan_hub_lists_emit(*spans, nh, nc, *[L.ptr(t) for t in out], L.ptr(ws), ws.numel(), L.stream_ptr()),
+            "tfgx_plan_hub_lists_emit")
+    return out
+
+
 def build_hub_lists(span_begin, span_end, threshold, chunk):
     """Cut every span [begin[r], end[r]) longer than `threshold` into chunks of `chunk` CSR positions.
-    -> (rows, chunk_ptr, chunk_begin, chunk_end, chunk_row) int32 device tensors, or None if no span is that long."""
+    -> (rows, chunk_ptr, chunk_begin, chunk_end, chunk_row) int32 device tensors, or None if no span is that long.
+    The torch statement of the lists (plans build them with build_hub_lists_device; the CPU test backend uses this)."""
     length = (span_end - span_begin)
     hub_rows = torch.nonzero(length > threshold).flatten()
     if hub_rows.numel() == 0:
