@@ -336,3 +336,45 @@ def test_max_pool_sage_layer0_backward_on_a_graph_without_edges(tfg):
     for k in ("mlp_kernel", "mlp_bias"):
         assert grads[k] is None or float(grads[k].abs().max()) == 0.0
     assert float(grads["self_kernel"].abs().max()) > 0.0
+
+
+@pytest.mark.parametrize("n_dst,mean", [(1, False), (1, True), (5, False), (5, True)])
+def test_self_loop_gradients_on_a_rectangular_plan(tfg, n_dst, mean):
+    """out = (1/cnt) (sum_i w_i x[col_i] + self_coef * x[:n_dst]) on an n_dst x n_src plan with n_dst < n_src: the self-loop
+    term's d/dx belongs to the first n_dst source rows only, and d/dself_coef is <x[:n_dst], g> per row.  Found by
+    tests/test_gpu_fuzz_backward.py (aggregate sweep, seeds 6 / 7 / 15): with n_dst = 1 the [n_dst, F] term was broadcast
+    onto EVERY source row, with 1 < n_dst < n_src the backward raised a shape error."""
+    from tf_geometric_amd import autograd as AG
+    from tf_geometric_amd.plan import CsrPlan
+    L = tfg._lib
+    rng = np.random.Generator(np.random.PCG64(31 + n_dst))
+    n_src, f, e = 40, 12, 90
+    ei = np.stack([rng.integers(0, n_dst, e), rng.integers(0, n_src - 8, e)]).astype(np.int32)   # sources 32.. unreferenced
+    x = rng.standard_normal((n_src, f)).astype(np.float32)
+    sc = rng.uniform(0.1, 1.0, n_dst).astype(np.float32)
+    g = rng.standard_normal((n_dst, f)).astype(np.float32)
+    plan = CsrPlan.build(L.as_i32(ei), n_dst, n_src)
+    xt = L.as_f32(x).requires_grad_(True)
+    st = L.as_f32(sc).requires_grad_(True)
+    out = AG.aggregate(plan, xt, L.MEAN if mean else L.SUM, self_coef=st)
+    out.backward(L.as_f32(g))
+    xr = torch.tensor(x, dtype=torch.float64, requires_grad=True)
+    sr = torch.tensor(sc, dtype=torch.float64, requires_grad=True)
+    row, col = torch.from_numpy(ei[0]).long(), torch.from_numpy(ei[1]).long()
+    ref = torch.zeros(n_dst, f, dtype=torch.float64).index_add(0, row, xr[col]) + sr[:, None] * xr[:n_dst]
+    if mean:
+        ref = ref / torch.bincount(row, minlength=n_dst).clamp(min=1).double()[:, None]
+    ref.backward(torch.from_numpy(g).double())
+    assert_parity(out.detach().cpu().numpy(), ref.detach().numpy(), what="forward")
+    assert_parity(xt.grad.cpu().numpy(), xr.grad.numpy(), what="d/dx")
+    assert_parity(st.grad.cpu().numpy(), sr.grad.numpy(), what="d/dself_coef")
+    assert float(xt.grad[n_src - 8:].abs().max()) == 0.0          # unreferenced sources past n_dst: no gradient at all
+
+
+@pytest.mark.parametrize("seed", [6, 7, 15])
+def test_fuzz_backward_rectangular_self_loop_seeds(tfg, monkeypatch, seed):
+    """The backward-sweep seeds that exposed the rectangular self-loop gradient (see the test above), kept as they were drawn."""
+    from test_gpu_fuzz_backward import test_fuzz_aggregate_backward, draw_aggregate
+    d = draw_aggregate(seed)
+    assert d["self"] and d["n_dst"] < d["n_src"] and d["need"]["x"]
+    test_fuzz_aggregate_backward(tfg, monkeypatch, seed)

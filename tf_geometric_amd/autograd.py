@@ -107,7 +107,8 @@ def _aggregate_grad_x(plan, mean, g, w_csr, self_coef):
         return segment_reduce(pt, g, L.SUM, w_csr=w_t, self_coef=self_coef.detach()), g
     gx = segment_reduce(pt, g, L.SUM, w_csr=w_t)
     if self_coef is not None:
-        gx = gx + self_coef.detach().unsqueeze(1) * g
+        # rectangular plan (n_dst < n_src): only the first n_dst sources carry a self-loop term
+        gx[:plan.n_dst] += self_coef.detach().unsqueeze(1) * g
     return gx, g
 
 
@@ -156,7 +157,7 @@ def _aggregate_backward(plan, mean, x, w_csr, self_coef, g, need_x, need_w, need
                                        int(x2.shape[1]), L.ptr(gw), None if hub_w is None else ctypes.byref(hub_w),
                                        L.stream_ptr()), "tfgx_sddmm_hub_f32")
     if need_s:
-        gs = (x.detach() * g).sum(1)
+        gs = (x.detach()[:plan.n_dst] * g).sum(1)
     return gx, gw, gs
 
 
