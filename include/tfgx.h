@@ -225,13 +225,31 @@ typedef struct tfgx_reduce_args {
        passes for a power-law plan at widths that are not a power of two: its walk is mostly short rows, whose start-up is
        paid once per pass).  Results do not depend on it. */
     int32_t wide_blocks;
-    int32_t reserved_r5;
+    /* Verified split route (tfgx_segment_reduce_f32 only): 0 = off, and then nothing below is read — a host built against
+       the struct without the members below (zeroed reserved slot) keeps its behaviour.  1 = x / x_tail / edge_tail are a
+       split layout built from the caller's dense table verify_x[n_verify, ld_verify_x] (16-byte aligned rows, ld % 4 == 0)
+       that may have been written to since, behind the host's back.  The launch
+         (1) compares every row of verify_x bit for bit with the layout's row — fused into the self-loop term when
+             self_coef is given and n_verify == n_dst (that term then reads verify_x), else a compare pass in front of the
+             gather — and sets *verify_word = 1 on any mismatch (a device uint32 owned by the caller, never cleared here);
+         (2) gathers from the layout;
+         (3) enqueues a repair launch: a compact grid that reads *verify_word and exits, or, when it is set, recomputes the
+             whole of out from verify_x on the plain route (bit-identical to a launch with x = verify_x and no layout).
+       No host synchronisation; the host learns of a mismatch by reading the word back (asynchronously) after the launch.
+       Needs edge_tail, accumulate = 0, no track, no hub lists. */
+    int32_t verify;
+    const float* verify_x;
+    int64_t ld_verify_x;
+    int64_t n_verify;
+    uint32_t* verify_word;
 } tfgx_reduce_args;
 
 int tfgx_segment_reduce_f32(const tfgx_reduce_args* args /* host */, tfgx_stream_t stream);
 
 /* The kernel symbol tfgx_segment_reduce_f32 would launch for `args` (template arguments as rocprofv3 prints them:
-   seg_reduce_kernel<VEC, G, CH, IS_MAX, WEIGHTED, SPLIT, TRACK>), written NUL-terminated into buf.  Host-only, launches
+   seg_reduce_kernel<VEC, G, CH, IS_MAX, WEIGHTED, SPLIT, TRACK, U>; the verified split route:
+   seg_reduce_verify_kernel<VEC, G, CH, IS_MAX, WEIGHTED, U> + repair, with "compare + " in front when the check is not
+   fused), written NUL-terminated into buf.  Host-only, launches
    nothing: measurement code (bench.py's roofline.kernel) names the kernel from the dispatch itself. */
 int tfgx_segment_reduce_describe(const tfgx_reduce_args* args /* host */, char* buf, size_t buf_bytes);
 

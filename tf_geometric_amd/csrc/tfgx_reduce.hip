@@ -72,6 +72,9 @@ struct KArgs {
     const float* edge_tail;  // optional with SPLIT: the tail columns of every edge's SOURCE row, in this plan's edge order
     int64_t ld_edge_tail;    // (streamed next to col / w instead of gathered: one line request fewer per edge)
     int32_t wide_blocks;     // tfgx_reduce_args.wide_blocks: 0 = library policy, 1 = column blocks, -1 = one burst per row
+    const float* verify_x;   // verified split route, fused check: the caller's dense table the layout was built from (the
+    int64_t ld_verify_x;     // self-loop term reads it, and compares it bit for bit with the layout's row)
+    uint32_t* verify_word;   // set to 1 on a mismatch (never cleared here); the repair launch runs only when it is set
 };
 
 #ifndef TFGX_REDUCE_GRID_CAP_DEFAULT
@@ -87,7 +90,7 @@ struct KArgs {
 #define TFGX_UNROLL_CH4 2
 #endif
 
-template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT, bool TRACK, int U>
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT, bool TRACK, int U, bool VERIFY>
 __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s, int e, int cj_next, float wj_next, int lane,
                                                const int (&coff)[CH], const bool (&cvalid)[CH], const float* const (&xb)[CH],
                                                const int64_t (&xl)[CH], const float* const (&xs)[CH],
@@ -99,8 +102,10 @@ __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s,
 // backward reads that instead of a float count array and an int32 position array (rows up to 65535 edges: longer rows are
 // hub rows and take the chunked path, which does not track).
 // U: edges per batch (0 = the default for the group shape: 8, 4 / 2 with several column chunks per lane).
-template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT = false, bool TRACK = false, int U = 0>
-__global__ __launch_bounds__(kBlock) void seg_reduce_kernel(const KArgs a)
+// VERIFY (with SPLIT and edge_tail): the self-loop term of the epilogue reads the caller's table a.verify_x instead of the
+// layout and compares the two rows bit for bit (see seg_reduce_verify_kernel below).
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT, bool TRACK, int U, bool VERIFY>
+__device__ __forceinline__ void seg_reduce_walk(const KArgs& a)
 {
     constexpr int ROWS_PER_BLOCK = kBlock / G;
     constexpr int COLS_PER_PASS = G * VEC * CH;
@@ -197,13 +202,63 @@ __global__ __launch_bounds__(kBlock) void seg_reduce_kernel(const KArgs a)
         float wj_next = wj_first;
         s = s1; e = e1; s1 = s2; e1 = e2; cj_first = cj_first1; wj_first = wj_first1;      // rotate the pipeline
         if (a.hub_threshold > 0 && e_cur - s_cur > a.hub_threshold) continue;   // handled by the chunked hub path
-        seg_reduce_row<VEC, G, CH, IS_MAX, WEIGHTED, SPLIT, TRACK, U>(a, row_of(r), s_cur, e_cur, cj_next, wj_next, lane, coff,
-                                                                      cvalid, xb, xl, xs, xsl, by_edge, init);
+        seg_reduce_row<VEC, G, CH, IS_MAX, WEIGHTED, SPLIT, TRACK, U, VERIFY>(a, row_of(r), s_cur, e_cur, cj_next, wj_next, lane,
+                                                                              coff, cvalid, xb, xl, xs, xsl, by_edge, init);
     }
 }
 
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT = false, bool TRACK = false, int U = 0>
+__global__ __launch_bounds__(kBlock) void seg_reduce_kernel(const KArgs a)
+{
+    seg_reduce_walk<VEC, G, CH, IS_MAX, WEIGHTED, SPLIT, TRACK, U, false>(a);
+}
+
+// The VERIFIED split route (tfgx_reduce_args.verify): the gathers read the split layout (main rows + edge-resident tail) like
+// seg_reduce_kernel<.., SPLIT = true, ..>, and the epilogue, which reads the destination's own row for the self-loop term
+// anyway, reads it from the caller's dense table verify_x AND from the layout and compares the two bit for bit.  On a
+// square plan every row of the table is compared exactly once per launch (4F sequential bytes per row next to ~50 gathered
+// 400-byte rows at products shape).  Any mismatch sets *verify_word = 1 (a vector store; the word is never cleared here).
+// The self-loop term uses the value from verify_x: whenever the check passes the two are equal.
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, int U = 0>
+__global__ __launch_bounds__(kBlock) void seg_reduce_verify_kernel(const KArgs a)
+{
+    seg_reduce_walk<VEC, G, CH, IS_MAX, WEIGHTED, true, false, U, true>(a);
+}
+
+// Enqueued after every verified launch, no host synchronisation in between: a compact grid-stride launch that reads the word
+// and exits; when it is set, it recomputes the whole output from the caller's table on the PLAIN route (a.x = verify_x, no
+// split layout: the same per-element FMA chains as seg_reduce_kernel<.., SPLIT = false, ..>, hence the same bits).
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, int U = 0>
+__global__ __launch_bounds__(kBlock) void seg_reduce_repair_kernel(const KArgs a)
+{
+    if (*a.verify_word == 0u) return;
+    seg_reduce_walk<VEC, G, CH, IS_MAX, WEIGHTED, false, false, U, false>(a);
+}
+
+// The standalone form of the check, in front of the gather, for verified launches whose epilogue does not read every row of
+// the table (no self-loop term, hub rows, or a table with more rows than the plan has destinations): one thread per
+// (row, 4 columns), grid-stride.
+__global__ __launch_bounds__(kBlock) void split_rows_compare_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int F,
+                                                                    int f_main, const float* __restrict__ xm, int64_t ldm,
+                                                                    const float* __restrict__ xt, int64_t ldt,
+                                                                    uint32_t* __restrict__ word)
+{
+    const int per_row = F / 4;
+    const int64_t total = n * per_row;
+    bool bad = false;
+    for (int64_t t = blockIdx.x * int64_t(kBlock) + threadIdx.x; t < total; t += int64_t(gridDim.x) * kBlock) {
+        const int64_t i = t / per_row;
+        const int j = int(t - i * per_row) * 4;
+        const uint4 u = *reinterpret_cast<const uint4*>(x + i * ldx + j);
+        const uint4 v = j < f_main ? *reinterpret_cast<const uint4*>(xm + i * ldm + j)
+                                   : *reinterpret_cast<const uint4*>(xt + i * ldt + (j - f_main));
+        bad = bad || u.x != v.x || u.y != v.y || u.z != v.z || u.w != v.w;
+    }
+    if (bad) *word = 1u;
+}
+
 // One destination row [s, e) of the plan, reduced by a group of G lanes (body of seg_reduce_kernel).
-template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT, bool TRACK, int U>
+template <int VEC, int G, int CH, bool IS_MAX, bool WEIGHTED, bool SPLIT, bool TRACK, int U, bool VERIFY>
 __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s, int e, int cj_next, float wj_next, int lane,
                                                const int (&coff)[CH], const bool (&cvalid)[CH], const float* const (&xb)[CH],
                                                const int64_t (&xl)[CH], const float* const (&xs)[CH],
@@ -341,6 +396,7 @@ __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s,
 
         // ---- epilogue (per destination row) ----
         const float sc = a.self_coef ? a.self_coef[r] : 0.0f;
+        bool mismatch = false;       // VERIFY: this lane's slice of the row differs between verify_x and the layout
         float divisor = 1.0f;
         if (a.op == TFGX_MEAN) {
             const int cnt = a.mean_count ? a.mean_count[r] : (e - s);
@@ -365,7 +421,13 @@ __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s,
             }
             if (a.self_coef) {
                 float xself[VEC];
-                if constexpr (SPLIT) load_vec<VEC>(xs[k] + r * xsl[k], xself);
+                if constexpr (VERIFY) {
+                    float xlay[VEC];
+                    load_vec<VEC>(a.verify_x + r * a.ld_verify_x + coff[k], xself);
+                    load_vec<VEC>(xs[k] + r * xsl[k], xlay);
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) mismatch = mismatch || __float_as_uint(xself[v]) != __float_as_uint(xlay[v]);
+                } else if constexpr (SPLIT) load_vec<VEC>(xs[k] + r * xsl[k], xself);
                 else load_vec<VEC>(a.x + r * a.ldx + coff[k], xself);
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
@@ -432,6 +494,9 @@ __device__ __forceinline__ void seg_reduce_row(const KArgs& a, int64_t r, int s,
                 }
             }
         }
+        if constexpr (VERIFY) {
+            if (mismatch) *a.verify_word = 1u;
+        }
     }
 }
 
@@ -489,6 +554,17 @@ int launch_cfg(const KArgs& a, bool is_max, bool weighted, int ny, hipStream_t s
     dim3 grid(grid_for(a.n_dst, ROWS_PER_BLOCK, CH >= 2 ? (reduce_grid_cap() < 4096 ? reduce_grid_cap() : 4096) : reduce_grid_cap()), ny, 1);
     dim3 block(kBlock, 1, 1);
     if constexpr (VEC == 4 && CH == 1) {
+        if (a.x_tail != nullptr && a.verify_x != nullptr) {     // verified split route, check fused into the epilogue
+            if (is_max) {
+                if (weighted) seg_reduce_verify_kernel<VEC, G, CH, true, true, U><<<grid, block, dummy_lds_bytes(), stream>>>(a);
+                else seg_reduce_verify_kernel<VEC, G, CH, true, false, U><<<grid, block, dummy_lds_bytes(), stream>>>(a);
+            } else {
+                if (weighted) seg_reduce_verify_kernel<VEC, G, CH, false, true, U><<<grid, block, dummy_lds_bytes(), stream>>>(a);
+                else seg_reduce_verify_kernel<VEC, G, CH, false, false, U><<<grid, block, dummy_lds_bytes(), stream>>>(a);
+            }
+            TFGX_LAUNCH_CHECK("seg_reduce_verify_kernel");
+            return TFGX_OK;
+        }
         if (a.x_tail != nullptr) {   // split rows: sum / mean only (the case that matters: 400-byte rows)
             if (is_max) {
                 if (weighted) seg_reduce_kernel<VEC, G, CH, true, true, true, false, U><<<grid, block, dummy_lds_bytes(), stream>>>(a);
@@ -524,6 +600,54 @@ int launch_cfg(const KArgs& a, bool is_max, bool weighted, int ny, hipStream_t s
     }
     TFGX_LAUNCH_CHECK("seg_reduce_kernel");
     return TFGX_OK;
+}
+
+// Workgroups of a compact grid for kernel `k`: what the device holds at once (CUs x resident workgroups per CU), computed on
+// the first launch of each kernel (*blocks caches it).  The repair launch is a grid-stride walk: on the happy path every
+// workgroup reads one word and exits.
+template <typename K>
+int resident_grid(K k, int* blocks)
+{
+    if (*blocks == 0) {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kBlock, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
+        *blocks = cus * per_cu;
+    }
+    return *blocks;
+}
+
+template <int G>
+int launch_repair_g(const KArgs& a, bool is_max, bool weighted, hipStream_t stream)
+{
+    static int blocks[4] = {0, 0, 0, 0};
+    auto go = [&](auto kernel, int slot) {
+        kernel<<<dim3(resident_grid(kernel, &blocks[slot]), 1, 1), dim3(kBlock, 1, 1), 0, stream>>>(a);
+    };
+    if (is_max) {
+        if (weighted) go(seg_reduce_repair_kernel<4, G, 1, true, true>, 0);
+        else go(seg_reduce_repair_kernel<4, G, 1, true, false>, 1);
+    } else {
+        if (weighted) go(seg_reduce_repair_kernel<4, G, 1, false, true>, 2);
+        else go(seg_reduce_repair_kernel<4, G, 1, false, false>, 3);
+    }
+    TFGX_LAUNCH_CHECK("seg_reduce_repair_kernel");
+    return TFGX_OK;
+}
+
+// The repair launch of the verified route: the plain route over the caller's table (4-float vectors, one column chunk per
+// lane: the shapes the split route runs at), G lanes per row.
+int launch_repair(const KArgs& a, int G, bool is_max, bool weighted, hipStream_t stream)
+{
+    switch (G) {
+        case 4: return launch_repair_g<4>(a, is_max, weighted, stream);
+        case 8: return launch_repair_g<8>(a, is_max, weighted, stream);
+        case 16: return launch_repair_g<16>(a, is_max, weighted, stream);
+        case 32: return launch_repair_g<32>(a, is_max, weighted, stream);
+        default: return launch_repair_g<64>(a, is_max, weighted, stream);
+    }
 }
 
 // Group shape of a launch: lanes per row G, column chunks per lane CH, column blocks on grid.y NY, edges per batch U
@@ -677,6 +801,13 @@ extern "C" int tfgx_segment_reduce_describe(const tfgx_reduce_args* p, char* buf
     a.F = int32_t(p->F); a.ldx = p->ldx; a.x = p->x; a.x_tail = p->x_tail; a.wide_blocks = p->wide_blocks;
     const GroupShape g = group_shape(a, vec);
     const bool split = p->x_tail != nullptr && vec == 4 && g.CH == 1;
+    if (p->verify && split) {
+        const bool fused = p->self_coef != nullptr && p->n_verify == p->n_dst;
+        snprintf(buf, buf_bytes, "%sseg_reduce_verify_kernel<%d, %d, %d, %s, %s, %d> + seg_reduce_repair_kernel",
+                 fused ? "" : "split_rows_compare_kernel + ", vec, g.G, g.CH, p->op == TFGX_MAX ? "true" : "false",
+                 p->w ? "true" : "false", g.U);
+        return TFGX_OK;
+    }
     snprintf(buf, buf_bytes, "seg_reduce_kernel<%d, %d, %d, %s, %s, %s, %s, %d>", vec, g.G, g.CH, p->op == TFGX_MAX ? "true" : "false",
              p->w ? "true" : "false", split ? "true" : "false", p->track ? "true" : "false", g.U);
     return TFGX_OK;
@@ -736,6 +867,34 @@ extern "C" int tfgx_segment_reduce_f32(const tfgx_reduce_args* p, tfgx_stream_t 
     hipStream_t stream = as_stream(stream_);
 
     int vec = vector_width(p);
+    a.verify_x = nullptr; a.ld_verify_x = 0; a.verify_word = nullptr;
+    if (p->verify) {
+        // verified split route: (1) the check, fused into the epilogue or in front, (2) the gather, (3) the repair launch
+        TFGX_REQUIRE(p->x_tail && p->edge_tail && p->verify_x && p->verify_word && p->n_verify >= 0,
+                     "verify: needs the split layout with edge_tail, verify_x and verify_word");
+        TFGX_REQUIRE(!p->accumulate && !p->track && !use_hub, "verify: no accumulate / track / hub lists");
+        TFGX_REQUIRE(p->ld_verify_x >= p->F && p->ld_verify_x % 4 == 0 && aligned_to(p->verify_x, 16) &&
+                         aligned_to(p->verify_word, 4),
+                     "verify: verify_x needs 16-byte aligned rows");
+        const GroupShape g = group_shape(a, vec);
+        TFGX_REQUIRE(vec == 4 && g.CH == 1, "verify: the split layout needs 16-byte aligned rows and F <= 256");
+        a.verify_word = p->verify_word;
+        if (p->self_coef != nullptr && p->n_verify == p->n_dst) {
+            a.verify_x = p->verify_x;
+            a.ld_verify_x = p->ld_verify_x;
+        } else if (p->n_verify > 0) {
+            split_rows_compare_kernel<<<grid_for(p->n_verify * (p->F / 4), kBlock, 8192), kBlock, 0, stream>>>(
+                p->verify_x, p->ld_verify_x, p->n_verify, int(p->F), int(p->f_main), p->x, p->ldx, p->x_tail, p->ld_tail,
+                p->verify_word);
+            TFGX_LAUNCH_CHECK("split_rows_compare_kernel");
+        }
+        int rc = launch_any(a, vec, is_max, weighted, stream);
+        if (rc != TFGX_OK) return rc;
+        KArgs r = a;              // the plain route over the caller's table
+        r.x = p->verify_x; r.ldx = p->ld_verify_x; r.x_tail = nullptr; r.ld_tail = 0; r.f_main = 0;
+        r.edge_tail = nullptr; r.ld_edge_tail = 0; r.verify_x = nullptr; r.ld_verify_x = 0;
+        return launch_repair(r, g.G, is_max, weighted, stream);
+    }
     int rc = launch_any(a, vec, is_max, weighted, stream);
     if (rc != TFGX_OK || !use_hub) return rc;
 

@@ -693,6 +693,97 @@ def release_relaid_copies():
     _RELAID.clear()
 
 
+# VERIFIED static layout of the plan-level entry (segment_reduce on a dense table): a table this plan meets
+# twice unchanged (same live storage, same torch version counter, same shape) is promoted to the split + edge-resident-tail
+# layout, held on the plan, under the layer path's policy (AUTO_STATIC_LAYOUT / TFGX_STATIC_LAYOUT=explicit, SplitRows.wanted,
+# TFGX_STATIC_LAYOUT_BUDGET).  It is served through the library's verified route (tfgx_reduce_args.verify): every launch
+# compares EVERY row of the table bit for bit with the layout on the device — fused into the self-loop term of the epilogue —
+# and a repair launch enqueued right after recomputes the whole output from the table on the plain route when anything
+# differed.  So a write the version counter never sees (a raw-pointer `out=`, an RCCL receive, x.data) cannot make a call
+# return stale results, and nothing waits for the device: the verify word is copied into pinned host memory after the launch
+# and read by a LATER call, which then demotes the layout for good (a table that keeps changing behind the counter pays the
+# check once and is never promoted again; a torch-visible write just drops the layout and counting starts again).  Nothing
+# is promoted, served or memoised inside a hipGraph capture.  The layout is freed when the table's storage dies.
+VERIFIED_STATS = {"promotions": 0, "served": 0, "demotions": 0}
+
+
+class _LayoutMemo(dict):
+    """data_ptr -> _VerifiedLayout of one plan (a dict type that finalizers can refer to weakly)."""
+
+
+class _VerifiedLayout(object):
+    __slots__ = ("store", "key", "rows", "word", "seen", "demoted", "__weakref__")
+
+    def __init__(self, store, key):
+        self.store, self.key = _weakref.ref(store), key
+        self.rows = self.word = self.seen = None
+        self.demoted = False
+
+    def drop(self):
+        self.rows = self.word = self.seen = None
+
+
+def _forget_layout(memo_ref, ptr, ent_ref):
+    """weakref.finalize callback: the table's storage died — free its layout."""
+    memo, ent = memo_ref(), ent_ref()
+    if memo is not None and ent is not None and memo.get(ptr) is ent:
+        del memo[ptr]
+        ent.drop()
+
+
+def verified_layout(plan, x, describe=False):
+    """The promoted layout (_VerifiedLayout) to serve the dense table `x` from on `plan`, or None: the plain route.  Records
+    the sighting (describe=True only looks)."""
+    if (not AUTO_STATIC_LAYOUT or _AUTO_SUPPRESSED[0] > 0 or not isinstance(x, torch.Tensor) or x.dim() != 2
+            or not x.is_cuda or x.dtype != torch.float32 or x.requires_grad or not x.is_contiguous() or x.data_ptr() % 16
+            or not SplitRows.wanted(int(x.shape[0]), int(x.shape[1])) or torch.cuda.is_current_stream_capturing()
+            or plan.hub_info() is not None):
+        return None
+    memo = plan.__dict__.get("_verified")
+    if memo is None:
+        if describe:
+            return None
+        memo = plan._verified = _LayoutMemo()
+    store = x.untyped_storage()
+    ptr, key = x.data_ptr(), (x._version, int(x.shape[0]), int(x.shape[1]))
+    ent = memo.get(ptr)
+    if ent is not None and ent.store() is not store:
+        ent = None                                   # another storage at a recycled address
+    if describe:
+        return ent if ent is not None and ent.rows is not None and ent.key == key and not ent.demoted else None
+    if ent is None:
+        if len(memo) >= 8:                           # hidden activations at ever new addresses: keep the promoted ones
+            for p in [p for p, e in memo.items() if e.rows is None and not e.demoted]:
+                del memo[p]
+        ent = memo[ptr] = _VerifiedLayout(store, key)
+        _weakref.finalize(store, _forget_layout, _weakref.ref(memo), ptr, _weakref.ref(ent))
+        return None
+    if ent.demoted:
+        return None
+    if ent.key != key:                               # written through torch: not static (yet) — count again from here
+        ent.drop()
+        ent.key = key
+        return None
+    if ent.rows is None:                             # second unchanged sighting: promote
+        F = int(x.shape[1])
+        need = 4 * (int(x.shape[0]) * F + plan.num_edges * (F % 32))
+        if need > static_layout_budget_bytes():
+            return None
+        ent.rows = SplitRows.from_dense(x).with_edge_tail(plan)
+        ent.word = torch.zeros(1, dtype=torch.int32, device=x.device)
+        ent.seen = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        VERIFIED_STATS["promotions"] += 1
+    elif int(ent.seen[0]) != 0:
+        # an earlier call's check failed (its repair launch already recomputed that call's output): demote for good.  The
+        # pinned word is written by the copy after every launch; the device word is never cleared, so any value read is one
+        # that some earlier call left — at worst the demotion comes a call later (and that call repairs too)
+        ent.drop()
+        ent.demoted = True
+        VERIFIED_STATS["demotions"] += 1
+        return None
+    return ent
+
+
 def wide_blocks_hint(explicit_spans, has_hub_lists, ldx, num_edges, n_rows):
     """tfgx_reduce_args.wide_blocks for one launch: 0 = the kernel's own choice (wide line-aligned rows gathered in 64-column
     blocks), -1 = one burst per gathered row.  ONE policy for every caller that fills a ReduceArgs
@@ -726,6 +817,12 @@ def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=
     sub-spans of the same rows (track_row_begin: the first position of the whole row)."""
     lib = L.require_gpu()
     split = x if isinstance(x, SplitRows) else None
+    verified = None
+    if (split is None and row_begin is None and row_end is None and col is None and track is None and not accumulate
+            and (n_dst is None or int(n_dst) == plan.n_dst)):
+        verified = verified_layout(plan, x, describe=describe)      # a promoted table: served from its layout, checked
+        if verified is not None:
+            table, split = x, verified.rows
     if split is not None:
         x, ldx = L.row_major_2d(split.main)
         F = split.shape[1]
@@ -769,6 +866,9 @@ def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=
         a.x_tail, a.ld_tail, a.f_main = split.tail.data_ptr(), int(split.tail.shape[1]), int(split.main.shape[1])
         if split.edge_tail is not None and split.edge_plan is plan and col is None:
             a.edge_tail, a.ld_edge_tail = split.edge_tail.data_ptr(), int(split.edge_tail.shape[1])
+    if verified is not None:
+        a.verify, a.verify_x, a.ld_verify_x = 1, table.data_ptr(), int(table.stride(0))
+        a.n_verify, a.verify_word = int(table.shape[0]), verified.word.data_ptr()
     if row_begin is None and row_end is None and col is None and n_dst == plan.n_dst and USE_ROW_ORDER and F <= ROW_ORDER_MAX_F:
         # skewed plans: degree-ordered walk (the rows sharing a wave have similar lengths).  Same-box A/B on R-MAT graphs:
         # F = 20: -7 .. -16 %, F = 64: -4 .. -11 % (round 2); round 4, after the hub finalize stopped being a latency chain
@@ -800,6 +900,9 @@ def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=
         return buf.value.decode()
     L.check(lib.tfgx_segment_reduce_f32(ctypes.byref(a), L.stream_ptr()), "tfgx_segment_reduce_f32")
     _AGG_LAUNCHES[0] += 1
+    if verified is not None:
+        verified.seen.copy_(verified.word, non_blocking=True)       # read by a later call (verified_layout)
+        VERIFIED_STATS["served"] += 1
     if given:
         written_by_kernel(out)
     if track is not None:
