@@ -174,7 +174,10 @@ typedef struct tfgx_reduce_args {
     int64_t ld_add;
     const int32_t* mean_count;/* [n_dst] or NULL: divisor for TFGX_MEAN (NULL: row_end-row_begin); <1 -> 1 */
     /* hub rows (only read when hub_threshold > 0 and n_hub_rows > 0); built once per plan by tfgx_plan_hub_lists_count /
-       _emit with the thresholds of tfgx_hub_policy */
+       _emit with the thresholds of tfgx_hub_policy.  REQUIRED: every hub_rows[i] < n_dst — the lists must be built for the
+       rows this launch reduces (n_rows = n_dst in _count / _emit).  The lists live on the device, so the host cannot check it;
+       the finalize pass writes out[hub_rows[i]], which for a row >= n_dst lies outside the launch (and may lie outside out).
+       A launch over the first rows of a larger plan passes no hub lists (hub_threshold = 0) or lists built for those rows. */
     const int32_t* hub_rows;        /* [n_hub_rows] destination ids with in-degree > hub_threshold, ascending */
     const int32_t* hub_chunk_ptr;   /* [n_hub_rows+1] chunk range of each hub row */
     const int32_t* hub_chunk_begin; /* [n_hub_chunks] CSR positions: chunk c covers [begin[c], end[c]) */
@@ -659,6 +662,24 @@ size_t tfgx_gemm_workspace_bytes(int64_t M, int64_t K, int64_t N);
 int tfgx_gemm_bias_act_cols_ws_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
                                    int32_t act, int64_t act_cols, float* C, int64_t ldc, int64_t M, int64_t K, int64_t N,
                                    void* workspace, size_t workspace_bytes, tfgx_stream_t stream);
+
+/* The route tfgx_gemm_bias_act_cols_ws_f32 takes for the same arguments, written NUL-terminated into buf (the call fails
+   with TFGX_ERR_INVALID_ARG when it does not fit; 200 bytes hold every route).  Host-only, launches nothing; the
+   pointers are looked at for alignment and for NULL, never dereferenced.  Computed by the dispatcher's own predicates:
+     gemm_rows_kernel<TN,bv4|b1> fixed | claimed     the row-streaming kernel, TN = ceil(N / 32), B staged with 16-byte or
+                                                     dword loads; "claimed" = its waves claim
+                                                     their tiles from the workspace's counters (needs a device with >= 32
+                                                     compute units, which a host-only call cannot see)
+     slices(S) x gemm_rows_kernel<4,...> ...           N = 128 S: the row kernel once per 128-column slice
+     gemm_skinny_kernel<NT>                          N <= 48 where the row kernel cannot go, NT = ceil(N / 16)
+     gemm_kernel<BM,BN,WM,WN,av4|a1,bv4|b1,ahead|step>   the LDS-tiled kernel: 16-byte or dword loads of A / B, operand
+                                                     read-ahead or per-step reads
+     split-K(S) gemm_kernel<...>                     the same cut into S slices of K (+ the ordered reduction)
+     remainder: <route of the first N - N % 128 columns> + <route of the rest>
+   Measurement and test code: a sweep asserts the route its draw was built for. */
+int tfgx_gemm_describe(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int32_t act,
+                       int64_t act_cols, const float* C, int64_t ldc, int64_t M, int64_t K, int64_t N, void* workspace,
+                       size_t workspace_bytes, char* buf, size_t buf_bytes);
 
 /* Weight gradient of a dense layer (the backward of tfgx_gemm_bias_act_f32):
    dW[Ka, N] = X[M, Ka]^T @ G[M, N] and, when db != NULL, db[N] = column sums of G (the bias gradient), reduced over

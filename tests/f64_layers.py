@@ -261,24 +261,32 @@ def _gat(x32, ei, wq, bq, wk, bk, wv, bias, num_heads, G, x_grad, dtype, kink_ma
     return out, grads, G_eff.float()
 
 
-def gat_attention_f64(Q, K, V, row_ptr, col, heads, keep=None, rate=0.0):
+def gat_attention_f64(Q, K, V, row_ptr, col, heads, keep=None, rate=0.0, add_self_loop=True, scale_d=None, stats=False):
     """The fused attention (nn/conv/gat.py:73-89) over a CSR plan, differentiable: Q [n_dst, H*d], K [n_src, H*d],
-    V [n_src, H*dv] float64 leaves; row_ptr / col the plan's numpy arrays.  Edges in CSR order, then the self-loop (r, r)
-    of every destination r < n_dst at positions E .. E+n_dst-1 (gat.py:43); keep [E + n_dst, H] = the host restatement of
-    the attention-dropout mask (gat.py:85), applied as keep / (1 - rate).  Small graphs: plain index_add, no chunking."""
+    V [n_src, H*dv] float64 leaves; row_ptr / col the plan's numpy arrays.  Edges in CSR order, then (add_self_loop) the
+    self-loop (r, r) of every destination r < n_dst at positions E .. E+n_dst-1 (gat.py:43); keep [E + n_dst, H] = the host
+    restatement of the attention-dropout mask (gat.py:85), applied as keep / (1 - rate); scale_d: the scores are divided by
+    sqrt(scale_d) instead of sqrt(d).  stats=True also returns the softmax statistics [n_dst, 2H] = (row maximum,
+    denominator without the 1e-8) per head, as tfgx_gat_args.stats_ml stores them (a row without terms: l = 0, m unspecified).
+    Small graphs: plain index_add, no chunking."""
     n = int(row_ptr.shape[0]) - 1
     ar = torch.arange(n, dtype=torch.int64)
-    row = torch.cat([torch.repeat_interleave(ar, torch.from_numpy(row_ptr[1:] - row_ptr[:-1]).long()), ar])
-    col = torch.cat([torch.from_numpy(col).long(), ar])
+    row = torch.repeat_interleave(ar, torch.from_numpy(row_ptr[1:] - row_ptr[:-1]).long())
+    col = torch.from_numpy(col).long()
+    if add_self_loop:
+        row, col = torch.cat([row, ar]), torch.cat([col, ar])
     d, dv = Q.shape[1] // heads, V.shape[1] // heads
-    outs = []
+    outs, ml = [], []
     for h in range(heads):
-        s = (Q[row, h * d:(h + 1) * d] * K[col, h * d:(h + 1) * d]).sum(-1) / math.sqrt(d)
+        s = (Q[row, h * d:(h + 1) * d] * K[col, h * d:(h + 1) * d]).sum(-1) / math.sqrt(d if scale_d is None else scale_d)
         m = torch.full((n,), -1e30, dtype=torch.float64).scatter_reduce(0, row, s, "amax")
         p = torch.exp(s - m[row].detach())
-        den = torch.zeros(n, dtype=torch.float64).index_add(0, row, p) + 1e-8
+        l = torch.zeros(n, dtype=torch.float64).index_add(0, row, p)
+        den = l + 1e-8
         a = p / den[row]
         if keep is not None:
-            a = a * torch.as_tensor(keep[:, h], dtype=torch.float64) / (1.0 - rate)
+            a = a * torch.as_tensor(keep[:a.shape[0], h], dtype=torch.float64) / (1.0 - rate)
         outs.append(torch.zeros(n, dv, dtype=torch.float64).index_add(0, row, a[:, None] * V[col, h * dv:(h + 1) * dv]))
-    return torch.cat(outs, 1)
+        ml += [m.detach(), l.detach()]
+    out = torch.cat(outs, 1)
+    return (out, torch.stack(ml, 1)) if stats else out

@@ -83,6 +83,23 @@ def test_argument_validation_without_gpu():
     assert lib.tfgx_gemm_workspace_bytes(170000, 128, 256) == 0                       # short launches keep the fixed tile map
     assert lib.tfgx_gemm_bias_act_cols_ws_f32(None, 4, None, 4, None, 0, 9, None, 4, 2, 4, 4, None, 0, None) == 1
     assert b"act_cols" in lib.tfgx_last_error()
+    # tfgx_gemm_describe: host only, same argument checks as the launch, never writes past buf_bytes
+    al = 1 << 20
+    args = (al, 128, 2 * al, 256, None, 0, 0, 3 * al, 256, 1 << 18, 128, 256)
+    big = ctypes.create_string_buffer(b"\xff" * 200, 200)
+    assert lib.tfgx_gemm_describe(*args, None, 0, big, 200) == 0 and big.value == b"gemm_rows_kernel<8,bv4> fixed"
+    assert lib.tfgx_gemm_describe(*args, 4 * al, 4096, big, 200) == 0 and big.value == b"gemm_rows_kernel<8,bv4> claimed"
+    small = ctypes.create_string_buffer(b"\xff" * 16, 16)
+    assert lib.tfgx_gemm_describe(*args, None, 0, small, 8) == 1 and b"buffer too small" in lib.tfgx_last_error()
+    assert small.raw[0:1] == b"\x00" and small.raw[8:] == b"\xff" * 8             # empty string, nothing past buf_bytes
+    assert lib.tfgx_gemm_describe(*args, None, 0, None, 200) == 1 and lib.tfgx_gemm_describe(*args, None, 0, big, 0) == 1
+    assert lib.tfgx_gemm_describe(None, 128, 2 * al, 256, None, 0, 0, 3 * al, 256, 4, 128, 256, None, 0, big, 200) == 1
+    assert b"null pointer" in lib.tfgx_last_error()
+    assert lib.tfgx_gemm_describe(al, 128, 2 * al, 256, None, 0, 257, 3 * al, 256, 4, 128, 256, None, 0, big, 200) == 1
+    assert b"act_cols" in lib.tfgx_last_error()
+    assert lib.tfgx_gemm_describe(al, 127, 2 * al, 256, None, 0, 0, 3 * al, 256, 4, 128, 256, None, 0, big, 200) == 1
+    assert b"leading dimension" in lib.tfgx_last_error()
+    assert lib.tfgx_gemm_describe(None, 0, None, 0, None, 0, 0, None, 0, 0, 1, 1, None, 0, big, 200) == 0 and b"M = 0" in big.value
     assert lib.tfgx_segment_max_with_count_f32(None, None, None, 4, None, 2, 8, None, 8, None, 8, None) == 1
     assert lib.tfgx_segment_max_backward_w_f32(None, None, None, 4, None, 8, 8, None, 8, None, 4, None, None) == 1
     # phases outside {1, 2, 3}; and a fused aggregate -> GEMM shape that does not fit LDS is refused on the host

@@ -378,3 +378,28 @@ def test_fuzz_backward_rectangular_self_loop_seeds(tfg, monkeypatch, seed):
     d = draw_aggregate(seed)
     assert d["self"] and d["n_dst"] < d["n_src"] and d["need"]["x"]
     test_fuzz_aggregate_backward(tfg, monkeypatch, seed)
+
+
+def test_partial_plan_launch_leaves_hub_rows_past_n_dst_alone(tfg):
+    """segment_reduce(..., n_dst=k) over the first k rows of a larger plan whose hub lists name a row >= k: the hub finalize
+    pass used to write that row of `out` (past the launch; out of bounds when out has only k rows).  Such a launch now takes
+    no hub lists; rows < k match the whole-plan launch.  Found while writing tests/test_gpu_fuzz_forward.py (setting n_dst)."""
+    from tf_geometric_amd import plan as P
+    L = tfg._lib
+    rng = np.random.Generator(np.random.PCG64(77))
+    n, f, k = 12, 20, 3
+    row = np.concatenate([rng.integers(0, n, 60), np.full(50, 7), np.full(40, 1)]).astype(np.int32)     # hubs: row 7 (>= k) and row 1 (< k)
+    ei = np.stack([row, rng.integers(0, n, row.shape[0]).astype(np.int32)])
+    x = L.as_f32(rng.standard_normal((n, f)).astype(np.float32))
+    old = P.HUB_THRESHOLD, P.HUB_CHUNK
+    P.HUB_THRESHOLD, P.HUB_CHUNK = 16, 8
+    try:
+        plan = P.CsrPlan.build(L.as_i32(ei), n, n)
+        assert plan.hub_info() is not None and {1, 7} <= set(plan.hub_info()[0].tolist())
+        whole = P.segment_reduce(plan, x, L.SUM)
+        out = torch.full((n, f), float("nan"), device="cuda")
+        P.segment_reduce(plan, x, L.SUM, out=out, n_dst=k)
+        assert bool(torch.isnan(out[k:]).all()), "rows past n_dst were written"
+        assert_parity(out[:k].cpu().numpy(), whole[:k].cpu().numpy(), what="first rows of the plan")
+    finally:
+        P.HUB_THRESHOLD, P.HUB_CHUNK = old

@@ -19,6 +19,8 @@
 #include "tfgx_common.h"
 #include "tfgx_mfma.h"
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <type_traits>
 
 namespace tfgx {
@@ -1372,6 +1374,16 @@ inline unsigned int* rows_tile_counter(int64_t M, void* workspace, size_t worksp
 }
 
 inline size_t rows_lds_bytes(int64_t K, int tn) { return sizeof(float) * size_t(K) * size_t(tn * 32 + 8); }
+// workgroups the row kernel would launch before the per-device cap (one per CU), and whether a grid that size can run the
+// claimed tile order (see launch_gemm_rows: every one of the 16 pools needs a claimant)
+inline int64_t rows_wgs(int64_t M, int tn)
+{
+    const int64_t waves = (tn <= 4 ? rows_threads<1>() : rows_threads<8>()) / 64;
+    return ((M + 31) / 32 + waves - 1) / waves;
+}
+inline bool rows_claimable(int64_t grid_x) { return grid_x >= 32; }
+// B -> LDS with 16-byte loads (else dword loads): the row kernel's b_vec4 argument
+inline bool rows_b_vec4(const float* B, int64_t ldb) { return (ldb % 4 == 0) && aligned_to(B, 16); }
 
 template <int TN>
 int launch_gemm_rows(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int act, float* C,
@@ -1392,9 +1404,8 @@ int launch_gemm_rows(const float* A, int64_t lda, const float* B, int64_t ldb, c
     }
     const int cus = cus_of[dev];
     const int64_t n_tiles = (M + 31) / 32;
-    constexpr int kWaves = rows_threads<TN>() / 64;
-    const int64_t wgs = (n_tiles + kWaves - 1) / kWaves;
-    const int b_vec4 = (ldb % 4 == 0) && aligned_to(B, 16);
+    const int64_t wgs = rows_wgs(M, TN);
+    const int b_vec4 = rows_b_vec4(B, ldb);
     // one persistent workgroup per CU.  (Rounds 2-3 ran the narrow outputs, TN <= 2, with up to three per CU; the round-4
     // same-box sweep — TFGX_ROWS_WGS_MULT, profiles/r04_gemm_sweep.jsonl — has one per CU equal or faster on every narrow
     // shape: 2.4 M x 100 -> 16: 0.298 -> 0.265 ms, 170 k x 256 -> 40: 0.071 -> 0.063 (every workgroup stages B in LDS for
@@ -1410,7 +1421,7 @@ int launch_gemm_rows(const float* A, int64_t lda, const float* B, int64_t ldb, c
     // 0, 8, 16, 24 present.  Smaller launches (few CUs, few tiles) take the fixed tile map instead — a pool without a
     // claimant would leave its tiles of C unwritten.
     static_assert(rows_threads<TN>() / 64 >= 4, "the claimed tile order needs all four (wave & 3) pool slots per workgroup");
-    if (grid.x < 32) tile_counter = nullptr;
+    if (!rows_claimable(grid.x)) tile_counter = nullptr;
     if (tile_counter)
         TFGX_HIP_CHECK(hipMemsetAsync(tile_counter, 0, kRowsCounterBytes, stream));
     gemm_rows_kernel<TN><<<grid, block, rows_lds_bytes(K, TN), stream>>>(A, lda, B, ldb, bias, act, act_cols, C, ldc, M, K,
@@ -1589,6 +1600,30 @@ inline int splitk_factor(int64_t tiles, int64_t K)
     return s < 2 ? 1 : int(s);
 }
 
+// What a generic-kernel launch decides on the host — the ONE place (launch_gemm launches by it, tfgx_gemm_describe reports it).
+struct GenericCfg { bool av4, bv4, split, ahead; int k_chunk, ny; };
+inline GenericCfg generic_cfg(const float* A, int64_t lda, const float* B, int64_t ldb, int K, int N, bool wide_wave_tile,
+                              const void* split_ws, int splits)
+{
+    // developer A/B: TFGX_GEMM_UNALIGNED_V4=0 restores the dword loads for rows that are not 16-byte aligned
+    static const bool unaligned_v4 = [] { const char* e = std::getenv("TFGX_GEMM_UNALIGNED_V4"); return !(e && e[0] == '0'); }();
+    // measured (same box, TFGX_GEMM_UNALIGNED_V4 = 0 / 1): 173312 x 1433 -> 16: 0.379 -> 0.281 ms; 170000 x 1433 -> 256: 1.235 ->
+    // 1.155; 233000 x 602 -> 64: 0.238 -> 0.214; 100000 x 301 -> 40: 0.073 -> 0.059; but 233000 x 602 -> 16 / 8: 0.188 -> 0.206 /
+    // 0.176 -> 0.205 — narrow outputs of a medium K stay on the dword loads
+    GenericCfg c;
+    c.av4 = ((lda % 4 == 0) && aligned_to(A, 16)) || (unaligned_v4 && aligned_to(A, 4) && (N > 32 || K >= 1024));
+    c.bv4 = (ldb % 4 == 0) && aligned_to(B, 16);
+    c.split = split_ws != nullptr && splits > 1;
+    c.k_chunk = c.split ? int((((K + splits - 1) / splits) + 15) / 16 * 16) : K;
+    c.ny = c.split ? (K + c.k_chunk - 1) / c.k_chunk : 1;
+    // developer A/B: TFGX_GEMM_LDS_AHEAD=0 keeps the per-step operand reads at every K
+    static const bool lds_ahead = [] { const char* e = std::getenv("TFGX_GEMM_LDS_AHEAD"); return !(e && e[0] == '0'); }();
+    // wide wave tiles only (4 MFMAs per step): on the 32 x 64 / 64 x 32 wave tiles (2 MFMAs per 3 operand reads) the pinned
+    // order LOST 8 % (233 k x 602 -> 64: 0.225 -> 0.244 ms, 170 k x 1433 -> 64: 0.385 -> 0.402)
+    c.ahead = wide_wave_tile && lds_ahead && c.k_chunk >= 256;
+    return c;
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int act, float* C,
                 int64_t ldc, int64_t M, int K, int N, int act_cols, hipStream_t stream, float* split_ws = nullptr,
@@ -1601,27 +1636,15 @@ int launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, const 
         set_error("tfgx_gemm_bias_act_f32: too many tiles");
         return TFGX_ERR_INVALID_ARG;
     }
-    // developer A/B: TFGX_GEMM_UNALIGNED_V4=0 restores the dword loads for rows that are not 16-byte aligned
-    static const bool unaligned_v4 = [] { const char* e = std::getenv("TFGX_GEMM_UNALIGNED_V4"); return !(e && e[0] == '0'); }();
-    // measured (same box, TFGX_GEMM_UNALIGNED_V4 = 0 / 1): 173312 x 1433 -> 16: 0.379 -> 0.281 ms; 170000 x 1433 -> 256: 1.235 ->
-    // 1.155; 233000 x 602 -> 64: 0.238 -> 0.214; 100000 x 301 -> 40: 0.073 -> 0.059; but 233000 x 602 -> 16 / 8: 0.188 -> 0.206 /
-    // 0.176 -> 0.205 — narrow outputs of a medium K stay on the dword loads
-    const bool av4 = ((lda % 4 == 0) && aligned_to(A, 16)) || (unaligned_v4 && aligned_to(A, 4) && (N > 32 || K >= 1024));
-    const bool bv4 = (ldb % 4 == 0) && aligned_to(B, 16);
-    const bool split = split_ws != nullptr && splits > 1;
-    const int k_chunk = split ? int((((K + splits - 1) / splits) + 15) / 16 * 16) : K;
-    const int ny = split ? (K + k_chunk - 1) / k_chunk : 1;
+    const GenericCfg cfg = generic_cfg(A, lda, B, ldb, K, N, (WM / 32) * (WN / 32) >= 4, split_ws, splits);
+    const bool av4 = cfg.av4, bv4 = cfg.bv4, split = cfg.split, ahead = cfg.ahead;
+    const int k_chunk = cfg.k_chunk, ny = cfg.ny;
     float* out = split ? split_ws : C;
     const int64_t ldo = split ? N : ldc;
     const float* kb = split ? nullptr : bias;
     const int ka = split ? TFGX_ACT_NONE : act;
     dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(ny), 1), block(kBlock, 1, 1);
-    // developer A/B: TFGX_GEMM_LDS_AHEAD=0 keeps the per-step operand reads at every K
-    static const bool lds_ahead = [] { const char* e = std::getenv("TFGX_GEMM_LDS_AHEAD"); return !(e && e[0] == '0'); }();
-    // wide wave tiles only (4 MFMAs per step): on the 32 x 64 / 64 x 32 wave tiles (2 MFMAs per 3 operand reads) the pinned
-    // order LOST 8 % (233 k x 602 -> 64: 0.225 -> 0.244 ms, 170 k x 1433 -> 64: 0.385 -> 0.402)
     constexpr bool kWideWaveTile = (WM / 32) * (WN / 32) >= 4;
-    const bool ahead = kWideWaveTile && lds_ahead && k_chunk >= 256;
 #define TFGX_GEMM_GO(AV, BV)                                                                                              \
     do {                                                                                                                  \
         if (ahead)                                                                                                        \
@@ -1653,6 +1676,38 @@ static inline int64_t generic_tiles(int64_t M, int64_t N)
 {
     const int64_t bm = N <= 32 ? 256 : 128, bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
     return ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+}
+
+// split-K slices of a generic-kernel launch: splitk_factor's answer when the caller lent a workspace that holds the partials
+// The dispatcher's route predicates above the leaf kernels — ONE statement each, used by tfgx_gemm_bias_act_cols_ws_f32 and
+// by tfgx_gemm_describe.
+static inline bool ldc_fits_rows(int64_t ldc) { return ldc < (int64_t(1) << 25); }          // the row kernel's stores: 36 rows x ldc x 4 in 32 bits
+// K * N too large for LDS but a 128-column slice fits: the row kernel once per slice
+static inline bool route_slices(const float* A, int64_t lda, int64_t ldc, int64_t M, int64_t K, int64_t N)
+{
+    return ldc_fits_rows(ldc) && N > 128 && N <= 512 && N % 128 == 0 && !rows_ok(A, lda, M, K, N) && rows_ok(A, lda, M, K, 128);
+}
+static inline bool route_skinny(const float* A, int64_t lda, int64_t M, int64_t K, int64_t N)
+{
+    return skinny_ok(A, lda, M, K, N) && (skinny_mode() == 2 || !rows_ok(A, lda, M, K, N));
+}
+static inline bool route_rows(const float* A, int64_t lda, int64_t ldc, int64_t M, int64_t K, int64_t N)
+{
+    return ldc_fits_rows(ldc) && rows_ok(A, lda, M, K, N);
+}
+// N = q * 128 + r with a short remainder (r <= 64) on a long K: two products
+static inline bool route_remainder(int64_t M, int64_t K, int64_t N)
+{
+    return N > 128 && N % 128 != 0 && N % 128 <= 64 && K >= 256 && M >= 4096;
+}
+static inline int rows_tn(int64_t N) { return int((N + 31) / 32) < 8 ? int((N + 31) / 32) : 8; }
+static inline int skinny_nt(int64_t N) { return skinny_tiles(N) < 3 ? skinny_tiles(N) : 3; }
+
+static inline int generic_splits(int64_t M, int64_t K, int64_t N, const void* workspace, size_t workspace_bytes)
+{
+    const int splits = splitk_factor(generic_tiles(M, N), K);
+    if (workspace == nullptr || workspace_bytes < sizeof(float) * size_t(splits) * size_t(M) * size_t(N)) return 1;
+    return splits;
 }
 
 #if TFGX_ROWS_EXPERIMENT == 3
@@ -1717,8 +1772,7 @@ extern "C" int tfgx_gemm_bias_act_cols_ws_f32(const float* A, int64_t lda, const
     const int ac = int(act_cols);
     // K * N too large for LDS but a column slice fits (hidden -> hidden, 256 -> 256): run the row-streaming kernel once
     // per slice of 128 columns.  A is streamed once per slice; at these widths the MFMA time still dominates.
-    const bool ldc_ok = ldc < (int64_t(1) << 25);          // same for the stores (36 rows x ldc x 4)
-    if (ldc_ok && N > 128 && N <= 512 && N % 128 == 0 && !rows_ok(A, lda, M, K, N) && rows_ok(A, lda, M, K, 128)) {
+    if (route_slices(A, lda, ldc, M, K, N)) {
         for (int64_t n0 = 0; n0 < N; n0 += 128) {
             const int64_t ac_slice = act_cols > n0 ? (act_cols - n0 < 128 ? act_cols - n0 : 128) : 0;
             const int rc = tfgx_gemm_bias_act_cols_ws_f32(A, lda, B + n0, ldb, bias ? bias + n0 : nullptr, act, ac_slice,
@@ -1727,18 +1781,18 @@ extern "C" int tfgx_gemm_bias_act_cols_ws_f32(const float* A, int64_t lda, const
         }
         return TFGX_OK;
     }
-    if (skinny_ok(A, lda, M, K, N) && (skinny_mode() == 2 || !rows_ok(A, lda, M, K, N))) {
-        switch (skinny_tiles(N)) {
+    if (route_skinny(A, lda, M, K, N)) {
+        switch (skinny_nt(N)) {
             case 1: return launch_gemm_skinny<1>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream);
             case 2: return launch_gemm_skinny<2>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream);
             default: return launch_gemm_skinny<3>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream);
         }
     }
-    if (ldc_ok && rows_ok(A, lda, M, K, N)) {
+    if (route_rows(A, lda, ldc, M, K, N)) {
         unsigned int* ctr = rows_tile_counter(M, workspace, workspace_bytes);
 #define TFGX_ROWS_CASE(T) \
     case T: return launch_gemm_rows<T>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream, ctr)
-        switch ((N + 31) / 32) {
+        switch (rows_tn(N)) {
             TFGX_ROWS_CASE(1);
             TFGX_ROWS_CASE(2);
             TFGX_ROWS_CASE(3);
@@ -1754,7 +1808,7 @@ extern "C" int tfgx_gemm_bias_act_cols_ws_f32(const float* A, int64_t lda, const
     // that is 50 % or more padding (N = 160: 3/8 of all MFMA work).  The first q * 128 columns and the remainder are two products
     // — A is streamed once more, the remainder on a 32- / 64-column tile: 233 k x 602 -> 160 0.66 -> 0.51 ms (hipBLASLt 0.48).
     // Long K only: on a short K the second pass over A costs what the padding did.
-    if (N > 128 && N % 128 != 0 && N % 128 <= 64 && K >= 256 && M >= 4096) {
+    if (route_remainder(M, K, N)) {
         const int64_t n_main = N - N % 128;
         int rc = tfgx_gemm_bias_act_cols_ws_f32(A, lda, B, ldb, bias, act, act_cols < n_main ? act_cols : n_main, C, ldc, M, K,
                                                 n_main, workspace, workspace_bytes, stream_);
@@ -1764,14 +1818,92 @@ extern "C" int tfgx_gemm_bias_act_cols_ws_f32(const float* A, int64_t lda, const
                                               workspace, workspace_bytes, stream_);
     }
     // small M with a long K leaves most CUs idle: split K over blockIdx.y when the caller lent a workspace
-    int splits = splitk_factor(generic_tiles(M, N), K);
+    const int splits = generic_splits(M, K, N, workspace, workspace_bytes);
     float* ws = static_cast<float*>(workspace);
-    if (ws == nullptr || workspace_bytes < sizeof(float) * size_t(splits) * size_t(M) * size_t(N)) splits = 1;
     if (N <= 32)
         return launch_gemm<256, 32, 64, 32>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream, ws, splits);
     if (N <= 64)
         return launch_gemm<128, 64, 32, 64>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream, ws, splits);
     return launch_gemm<128, 128, 64, 64>(A, lda, B, ldb, bias, act, C, ldc, M, int(K), int(N), ac, stream, ws, splits);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// tfgx_gemm_describe: the route tfgx_gemm_bias_act_cols_ws_f32 takes for these arguments, as text.  Host code only; pointers
+// are looked at for alignment (and null-ness), never dereferenced.  It walks the dispatcher's own order with the dispatcher's
+// own predicates (route_slices / route_skinny / route_rows / route_remainder, rows_tn, skinny_nt, rows_b_vec4,
+// rows_tile_counter / rows_claimable, generic_splits, generic_cfg), so a route string is
+// what a launch with the same arguments runs.  One exception it cannot see without a device: the row kernel's claimed tile
+// order also needs 32 workgroups after the one-per-CU cap, i.e. a device with at least 32 compute units.
+static void describe_generic(std::string& s, int bm, int bn, int wm, int wn, const float* A, int64_t lda, const float* B, int64_t ldb,
+                             int64_t M, int64_t K, int64_t N, const void* workspace, size_t workspace_bytes)
+{
+    const int splits = generic_splits(M, K, N, workspace, workspace_bytes);
+    const GenericCfg c = generic_cfg(A, lda, B, ldb, int(K), int(N), (wm / 32) * (wn / 32) >= 4, workspace, splits);
+    char t[128];
+    if (c.split) {
+        snprintf(t, sizeof(t), "split-K(%d) ", c.ny);
+        s += t;
+    }
+    snprintf(t, sizeof(t), "gemm_kernel<%d,%d,%d,%d,%s,%s,%s>", bm, bn, wm, wn, c.av4 ? "av4" : "a1", c.bv4 ? "bv4" : "b1",
+             c.ahead ? "ahead" : "step");
+    s += t;
+}
+
+static void describe_route(std::string& s, const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc,
+                           int64_t M, int64_t K, int64_t N, void* workspace, size_t workspace_bytes)
+{
+    char t[64];
+    if (route_slices(A, lda, ldc, M, K, N)) {
+        snprintf(t, sizeof(t), "slices(%d) x ", int(N / 128));
+        s += t;
+        return describe_route(s, A, lda, B, ldb, C, ldc, M, K, 128, workspace, workspace_bytes);   // B + n0, C + n0: n0 % 128 == 0
+    }
+    if (route_skinny(A, lda, M, K, N)) {
+        snprintf(t, sizeof(t), "gemm_skinny_kernel<%d>", skinny_nt(N));
+        s += t;
+        return;
+    }
+    if (route_rows(A, lda, ldc, M, K, N)) {
+        const int tn = rows_tn(N);
+        const bool claimed = rows_tile_counter(M, workspace, workspace_bytes) != nullptr && rows_claimable(rows_wgs(M, tn));
+        snprintf(t, sizeof(t), "gemm_rows_kernel<%d,%s> %s", tn, rows_b_vec4(B, ldb) ? "bv4" : "b1", claimed ? "claimed" : "fixed");
+        s += t;
+        return;
+    }
+    if (route_remainder(M, K, N)) {
+        const int64_t n_main = N - N % 128;
+        s += "remainder: ";
+        describe_route(s, A, lda, B, ldb, C, ldc, M, K, n_main, workspace, workspace_bytes);
+        s += " + ";
+        return describe_route(s, A, lda, B + n_main, ldb, C + n_main, ldc, M, K, N - n_main, workspace, workspace_bytes);
+    }
+    if (N <= 32) return describe_generic(s, 256, 32, 64, 32, A, lda, B, ldb, M, K, N, workspace, workspace_bytes);
+    if (N <= 64) return describe_generic(s, 128, 64, 32, 64, A, lda, B, ldb, M, K, N, workspace, workspace_bytes);
+    return describe_generic(s, 128, 128, 64, 64, A, lda, B, ldb, M, K, N, workspace, workspace_bytes);
+}
+
+extern "C" int tfgx_gemm_describe(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int32_t act,
+                                  int64_t act_cols, const float* C, int64_t ldc, int64_t M, int64_t K, int64_t N,
+                                  void* workspace, size_t workspace_bytes, char* buf, size_t buf_bytes)
+{
+    (void)bias;
+    TFGX_REQUIRE(buf != nullptr && buf_bytes > 0, "null argument");
+    buf[0] = 0;
+    TFGX_REQUIRE(M >= 0 && K >= 1 && N >= 1, "bad M / K / N");
+    TFGX_REQUIRE(K < (int64_t(1) << 30) && N < (int64_t(1) << 30), "K / N too large");
+    TFGX_REQUIRE(act == TFGX_ACT_NONE || act == TFGX_ACT_RELU, "bad act");
+    TFGX_REQUIRE(act_cols >= 0 && act_cols <= N, "act_cols outside [0, N]");
+    std::string s;
+    if (M == 0) {
+        s = "nothing (M = 0)";
+    } else {
+        TFGX_REQUIRE(A && B && C, "null pointer");
+        TFGX_REQUIRE(lda >= K && ldb >= N && ldc >= N, "leading dimension too small");
+        describe_route(s, A, lda, B, ldb, C, ldc, M, K, N, workspace, workspace_bytes);
+    }
+    TFGX_REQUIRE(s.size() < buf_bytes, "buffer too small for the route text");
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return TFGX_OK;
 }
 
 extern "C" int tfgx_gemm_bias_act_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,

@@ -881,7 +881,10 @@ def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=
         a.track, a.ld_track = track.data_ptr(), int(track.stride(0))
         if track_row_begin is not None:      # positions relative to the WHOLE row when it is reduced span by span
             a.track_row_begin = track_row_begin.data_ptr()
-    hub = plan.hub_info() if (row_begin is None and row_end is None and col is None and track is None) else None
+    # (a launch over the first rows of a larger plan takes no hub lists: they name rows of the WHOLE plan, and the finalize
+    # pass would write the rows past n_dst; long rows are then walked inline — same sums)
+    hub = plan.hub_info() if (row_begin is None and row_end is None and col is None and track is None
+                              and n_dst == plan.n_dst) else None
     if hub is not None:
         hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
         scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=x.device)

@@ -41,6 +41,11 @@ def main(path):
     checked += 3
     assert lib.tfgx_gemm_bias_act_f32(None, 4, None, 4, None, 0, None, 4, 2, 0, 4, None) == 1
     assert lib.tfgx_gemm_bias_act_cols_ws_f32(None, 4, None, 4, None, 0, 9, None, 4, 2, 4, 4, None, 0, None) == 1
+    gbuf = ctypes.create_string_buffer(29)      # one byte short of the text below + NUL: refused, nothing written past it
+    assert lib.tfgx_gemm_describe(1 << 20, 128, 1 << 21, 256, None, 0, 0, 1 << 22, 256, 1 << 18, 128, 256, None, 0, gbuf, 29) == 1
+    gbuf = ctypes.create_string_buffer(30)      # exactly the text + NUL (29 + 1): one byte more written is a finding
+    assert lib.tfgx_gemm_describe(1 << 20, 128, 1 << 21, 256, None, 0, 0, 1 << 22, 256, 1 << 18, 128, 256, None, 0, gbuf, 30) == 0
+    assert gbuf.value == b"gemm_rows_kernel<8,bv4> fixed"
     assert lib.tfgx_gemm_workspace_bytes(2708, 1433, 256) > 0 and lib.tfgx_gemm_workspace_bytes(0, 1, 1) == 0
     assert lib.tfgx_gemm_tn_workspace_bytes(2400000, 100, 256, 1) > 0 and lib.tfgx_gemm_tn_workspace_bytes(5, 3000, 4, 0) > 0 and lib.tfgx_gemm_tn_workspace_bytes(0, 3, 4, 0) == 0
     assert lib.tfgx_gemm_tn_f32(None, 4, None, 4, 10, 4, 4, None, 4, None, None, 0, None) == 1
