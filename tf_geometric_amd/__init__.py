@@ -8,14 +8,29 @@ Only the hot path of the reference is here: aggregate_neighbors 
 the dense x @ W next to it, and dst-range sharding with halo exchange.  Compute = hand-written HIP kernels in
 lib/libtfgx.so (C ABI: include/tfgx.h); importing works without a GPU, calling an operator does not.
 """
+import torch as _torch
+
 from . import _lib
 from .activations import relu
-from .plan import CsrPlan, prepare_static_features, release_static_features
+from .plan import CsrPlan, prepare_static_features, release_static_features, HalfRows
 from .sparse import SparseMatrix
 from . import nn
 from . import layers
 from . import dist
 from . import utils
 from .graph_capture import CapturedForward, CapturedTrainStep
+
+
+def prepare_half_features(x, dtype=_torch.bfloat16):
+    """Store a float32 feature table in 16 bits (torch.bfloat16 by default, or torch.float16) for the aggregation kernels:
+    a HalfRows on the line-friendly row stride, quantised by tfgx_rows_f32_to_h16 (round to nearest even).  Arithmetic stays
+    float32; the result of every reduce over it equals the float32 route's on half_features_to_f32(h) bit for bit."""
+    return HalfRows.from_dense(x, dtype=dtype)
+
+
+def half_features_to_f32(h):
+    """The dense float32 [n, F] tensor a HalfRows stands for (exact)."""
+    return h.float()
+
 
 __version__ = "0.1.0"

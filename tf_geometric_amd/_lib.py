@@ -243,6 +243,20 @@ SIGNATURES = {
     "tfgx_plan_source_blocks": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }
 
+# include/tfgx_h16.h (16-bit feature tables): its own header, its own version, its own table — checked against that header by
+# tests/test_h16_abi.py.  tfgx.h and SIGNATURES above do not know these names.
+H16_ABI_VERSION = 1
+DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+H16_DTYPES = {torch.bfloat16: DT_BF16, torch.float16: DT_F16}
+H16_SIGNATURES = {
+    "tfgx_h16_version": (ctypes.c_int, []),
+    "tfgx_segment_reduce_h16": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I32, _P]),
+    "tfgx_segment_reduce_h16_describe": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I32, ctypes.c_char_p, ctypes.c_size_t]),
+    "tfgx_rows_f32_to_h16": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I32, _P]),
+    "tfgx_rows_h16_to_f32": (ctypes.c_int, [_P, _I64, _I32, _I64, _I64, _P, _I64, _P]),
+    "tfgx_h16_friendly_ld": (_I64, [_I64]),
+}
+
 _lib = None
 
 
@@ -266,6 +280,13 @@ def load_library():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in H16_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_h16_version() != H16_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_h16 ABI {} but this package binds {} (include/tfgx_h16.h): "
+                        "rebuild with __graft_entry__.build()".format(LIB_PATH, lib.tfgx_h16_version(), H16_ABI_VERSION))
     if lib.tfgx_version() != ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for ABI {} but this package binds ABI {} (include/tfgx.h "
                         "TFGX_ABI_VERSION): rebuild with __graft_entry__.build()".format(LIB_PATH, lib.tfgx_version(), ABI_VERSION))

@@ -25,11 +25,11 @@ import torch
 
 from . import _lib as L
 from .plan import (segment_reduce, can_track, gemm_bias_act, gemm_tn, transpose, SplitRows, gather_friendly_empty,
-                   gather_friendly_copy, aggregate_gemm, aggregate_gemm_applies, column_sums)
+                   gather_friendly_copy, aggregate_gemm, aggregate_gemm_applies, column_sums, HalfRows)
 
 
 def needs_grad(*tensors):
-    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+    return torch.is_grad_enabled() and any(isinstance(t, (torch.Tensor, HalfRows)) and t.requires_grad for t in tensors)
 
 
 def _transposed(plan):
@@ -518,9 +518,97 @@ def pool_mlp_max(plan, x, kernel, bias):
     return _PoolMlpMax.apply(plan, L.as_f32(x), L.as_f32(kernel), None if bias is None else L.as_f32(bias))
 
 
+class _HalfGradSink(torch.autograd.Function):
+    """The ONE place the gradient of a HalfRows.from_tensor(t) reaches t: every use of the table (aggregation, widening) sends
+    its float32 gradient to the same float32 [n, F] proxy (a stride-0 view: no table is allocated), autograd sums them in
+    float32, and this node rounds the sum to t.dtype once, to nearest even, as the last step."""
+
+    @staticmethod
+    def forward(ctx, src):
+        ctx.dtype, ctx.device = src.dtype, src.device
+        return torch.zeros((1, 1), dtype=torch.float32, device=L.device()).expand(int(src.shape[0]), int(src.shape[1]))
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.require_gpu()
+        g, ldg = L.row_major_2d(L.as_f32(g))
+        n, F = int(g.shape[0]), int(g.shape[1])
+        gx = torch.empty((n, F), dtype=ctx.dtype, device=g.device)       # dense: no copy off a padded stride afterwards
+        L.check(lib.tfgx_rows_f32_to_h16(L.ptr(g), ldg, n, F, L.ptr(gx), max(F, 1), L.H16_DTYPES[ctx.dtype], L.stream_ptr()),
+                "tfgx_rows_f32_to_h16")
+        return gx if gx.device == ctx.device else gx.to(ctx.device)
+
+
+def _half_grad_proxy(h):
+    """The float32 gradient sink of a HalfRows whose source requires grad (one per HalfRows), else None."""
+    if not needs_grad(h):
+        return None
+    proxy = getattr(h, "_grad_proxy", None)
+    if proxy is None:
+        proxy = h._grad_proxy = _HalfGradSink.apply(h.source)
+    return proxy
+
+
+class _WidenHalf(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, proxy):
+        return h.float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, g
+
+
+def widen(h):
+    """h.float() with a gradient: d/dt of HalfRows.from_tensor(t) flows through the widened tensor too (the self / identity
+    terms of aggregate_neighbors and the GraphSAGE layers), summed in float32 with the aggregation's and rounded once."""
+    proxy = _half_grad_proxy(h)
+    return h.float() if proxy is None else _WidenHalf.apply(h, proxy)
+
+
+class _AggregateHalf(torch.autograd.Function):
+    """_Aggregate over a HalfRows (16-bit storage): the forward is tfgx_segment_reduce_h16 — the float32 route's bits —, the
+    backward the existing float32 kernels on the float32 gradient; d/dx goes, in float32, to the table's gradient sink
+    (_HalfGradSink), which rounds to the table's type as the last step."""
+
+    @staticmethod
+    def forward(ctx, plan, mean, h, proxy, w_csr, self_coef, bias, act):
+        ctx.plan, ctx.mean, ctx.act, ctx.h = plan, mean, act, h
+        out = segment_reduce(plan, h, L.MEAN if mean else L.SUM, w_csr=w_csr,
+                             self_coef=None if self_coef is None else self_coef.detach(),
+                             bias=None if bias is None else bias.detach().contiguous(), act=act)
+        ctx.save_for_backward(w_csr, self_coef, bias, out if act == L.ACT_RELU else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        plan, h = ctx.plan, ctx.h
+        w_csr, self_coef, bias, out = ctx.saved_tensors
+        g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
+        gb = column_sums(g) if (bias is not None and ctx.needs_input_grad[6]) else None
+        need_x, need_s = ctx.needs_input_grad[3], ctx.needs_input_grad[5] and self_coef is not None
+        gx32, _, gs = _aggregate_backward(plan, ctx.mean, h.float() if need_s else None, w_csr, self_coef, g, need_x, False, need_s)
+        return None, None, None, gx32 if need_x else None, None, gs, gb, None
+
+
+def _aggregate_half(plan, h, op, w_csr, self_coef, bias, act, rows=None, max_passes=None):
+    if rows is not None or max_passes is not None:
+        raise TypeError("aggregate on a HalfRows takes neither rows= (the split-row layouts) nor max_passes= (the tracked max)")
+    if op == L.MAX:
+        if needs_grad(h, w_csr, self_coef, bias):
+            raise NotImplementedError("max aggregation over a 16-bit table is inference-only (the kernel keeps no track table)")
+        return segment_reduce(plan, h, L.MAX, w_csr=w_csr, self_coef=self_coef, bias=bias, act=act)
+    if isinstance(w_csr, torch.Tensor) and w_csr.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("edge weights that require grad are not supported over a 16-bit table (the SDDMM is float32-only)")
+    return _AggregateHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), None if w_csr is None else w_csr.detach(), self_coef,
+                                bias, act)
+
+
 def aggregate(plan, x, op, w_csr=None, self_coef=None, rows=None, bias=None, act=L.ACT_NONE, max_passes=None):
     """Differentiable gather-scale-segment-reduce (sum / mean / max) on `plan`; sum / mean take the layer's bias and
-    ReLU in the kernel epilogue (bias: a tensor that may require grad)."""
+    ReLU in the kernel epilogue (bias: a tensor that may require grad).  x may be a HalfRows (sum / mean; max without grad)."""
+    if isinstance(x, HalfRows):
+        return _aggregate_half(plan, x, op, w_csr, self_coef, bias, act, rows, max_passes)
     if op == L.MAX:
         if self_coef is not None:
             raise NotImplementedError("max aggregation with an implicit self-loop is inference-only")

@@ -355,6 +355,10 @@ def gat(x, edge_index,
     :return: [num_nodes, num_output_features]
     """
     lib = L.require_gpu()
+    from ...plan import HalfRows
+    if isinstance(x, HalfRows):
+        raise TypeError("gat multiplies x by its query / key / value kernels before aggregating: a HalfRows (16-bit table) is "
+                        "taken by the aggregation kernels only — 16-bit GEMM operands are out of scope; pass x.float()")
     drop = float(edge_drop_rate) if training else 0.0           # SparseMatrix.dropout(rate, training) (:85)
     if not 0.0 <= drop < 1.0:
         raise Exception("edge_drop_rate must be in [0, 1)")

@@ -175,6 +175,11 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     :return: [num_nodes, num_output_features]
     """
     L.require_gpu()
+    from ...plan import HalfRows
+    if isinstance(x, HalfRows):
+        raise TypeError("gcn multiplies x by its kernel before aggregating when units < num_features (and fuses the GEMM into "
+                        "the aggregation otherwise): a HalfRows (16-bit table) is taken by the aggregation kernels only — "
+                        "16-bit GEMM operands are out of scope; pass x.float()")
     xs = sparse_features(x)
     if xs is not None:
         # sparse node features (one-hot / bag-of-words rows; tf.sparse.sparse_dense_matmul, :269-270):

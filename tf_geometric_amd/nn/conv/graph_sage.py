@@ -15,10 +15,16 @@ import torch
 from ... import _lib as L
 from ...activations import resolve as _resolve_act
 from ...plan import (CsrPlan, segment_reduce, gemm_bias_act, l2_normalize_rows_, static_rows,
-                     static_aggregate, static_aggregate_applies, gather_friendly_empty, aggregate_gemm)
+                     static_aggregate, static_aggregate_applies, gather_friendly_empty, aggregate_gemm, HalfRows)
 from ...sparse import SparseMatrix
 from .gcn import gcn_norm_adj
 from ... import autograd as AG
+
+
+def _refuse_half(x, who):
+    if isinstance(x, HalfRows):
+        raise TypeError("{} multiplies x by a kernel before (or while) aggregating: a HalfRows (16-bit table) is taken by the "
+                        "aggregation kernels only — 16-bit GEMM operands are out of scope; pass x.float()".format(who))
 
 
 def _combine(from_x_kernel, x, from_neigh_kernel, reduced, bias, activation, concat, normalize):
@@ -123,7 +129,15 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
     reduce(w * x[col]) @ W_neigh == reduce(w * (x @ W_neigh)[col]): when the neighbour projection is NARROWER than the
     input (hidden layers: 256 -> units/2) the GEMM runs first and the gather moves 4*ku instead of 4*F bytes per edge —
     the same move as GCN's narrow-side aggregation; bias and activation ride in the aggregation's
-    epilogue and the result lands directly in its half of the output.  Same value up to fp32 re-association."""
+    epilogue and the result lands directly in its half of the output.  Same value up to fp32 re-association.
+    A HalfRows x (16-bit storage): the neighbour half aggregates on tfgx_segment_reduce_h16 into float32, the projections run
+    on the float32 GEMM, the self half reads x.float()."""
+    if isinstance(x, HalfRows):
+        n = int(x.shape[0])
+        plan = CsrPlan.from_cache(edge_index, n, n, cache)
+        w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
+        reduced = AG.aggregate(plan, x, op, w_csr) if AG.needs_grad(x, edge_weight) else segment_reduce(plan, x, op, w_csr=w_csr)
+        return _combine(L.as_f32(self_kernel), AG.widen(x), L.as_f32(neighbor_kernel), reduced, bias, activation, concat, normalize)
     x = L.as_f32(x)
     wn = L.as_f32(neighbor_kernel)
     ws = L.as_f32(self_kernel)
@@ -196,6 +210,7 @@ def sum_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel, bia
 
 def gcn_graph_sage(x, edge_index, edge_weight, kernel, bias=None, activation=None, normalize=False, cache=None):
     """Reference: graph_sage.py:118-161 (quirks kept, see module docstring)."""
+    _refuse_half(x, "gcn_graph_sage")
     x = L.as_f32(x)
     n = int(x.shape[0])
     ei = L.as_i32(edge_index)
@@ -255,6 +270,7 @@ def _pool_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_mlp_kerne
     if edge_weight is None:
         raise TypeError("edge_weight=None is not supported by the pooling aggregators "
                         "(gcn_mapper(None) fails in the reference, graph_sage.py:197/260)")
+    _refuse_half(x, "the pooling GraphSAGE aggregators")
     x = L.as_f32(x)
     n = int(x.shape[0])
     plan = CsrPlan.from_cache(edge_index, n, n, cache)

@@ -9,7 +9,7 @@ tensors -> segment-reduce kernel over the explicit messages.
 import torch
 
 from ... import _lib as L
-from ...plan import CsrPlan, segment_reduce
+from ...plan import CsrPlan, segment_reduce, HalfRows
 from ... import autograd as AG
 
 
@@ -78,6 +78,8 @@ def aggregate_neighbors(x, edge_index, edge_weight=None, mapper=identity_mapper,
     :param cache: optional dict holding the per-graph CSR plan (extension; the reference has no plan to cache)
     """
     L.require_gpu()
+    if isinstance(x, HalfRows):
+        return _aggregate_neighbors_half(x, edge_index, edge_weight, mapper, reducer, updater, num_nodes, cache)
     x = L.as_f32(x)
     ei = L.as_i32(edge_index)
     if ei.shape[0] == 0:                                    # :57 tests dimension 0 only: "no edges" given as []
@@ -102,3 +104,25 @@ def aggregate_neighbors(x, edge_index, edge_weight=None, mapper=identity_mapper,
     neighbor_msg = mapper(repeated_x, neighbor_x, edge_weight=edge_weight)     # :65
     reduced_msg = reducer(neighbor_msg, ei[0], num_nodes=n)                    # :70
     return updater(x, reduced_msg)                          # :71
+
+
+def _aggregate_neighbors_half(h, edge_index, edge_weight, mapper, reducer, updater, num_nodes, cache):
+    """aggregate_neighbors over a HalfRows (16-bit storage, float32 arithmetic and result): the fused triples only — an
+    arbitrary mapper would need the [E, F] messages in float32, which is what the 16-bit table is there to avoid."""
+    ei = L.as_i32(edge_index)
+    n = int(h.shape[0]) if num_nodes is None else int(num_nodes)
+    if not ((mapper in (identity_mapper, gcn_mapper)) and (reducer in _REDUCER_OPS) and (updater in (sum_updater, identity_updater))
+            and (updater is identity_updater or n == int(h.shape[0]))):
+        raise TypeError("aggregate_neighbors on a HalfRows supports identity_mapper / gcn_mapper x sum / mean / max reducer x "
+                        "sum_updater / identity_updater only; widen the table (h.float()) for an arbitrary mapper")
+    if ei.shape[0] == 0:
+        return h.float()
+    if mapper is gcn_mapper and edge_weight is None:
+        raise TypeError("gcn_mapper needs edge_weight (tf.expand_dims(None) in the reference, gcn.py:222)")
+    plan = CsrPlan.from_cache(ei, n, int(h.shape[0]), cache)
+    w_csr = AG.edge_attr_csr(plan, edge_weight, cache) if mapper is gcn_mapper else None
+    op = _REDUCER_OPS[reducer]
+    if AG.needs_grad(h, edge_weight):
+        red = AG.aggregate(plan, h, op, w_csr)
+        return AG.widen(h) + red if updater is sum_updater else red
+    return segment_reduce(plan, h, op, w_csr=w_csr, add_x=h.float() if updater is sum_updater else None)

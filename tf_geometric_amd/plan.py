@@ -301,6 +301,186 @@ class SplitRows(object):
         return out
 
 
+class HalfRows(object):
+    """A 16-bit feature table (torch.bfloat16 / torch.float16 STORAGE, float32 arithmetic): `table` is a [n, ld] device
+    tensor with 16-byte aligned rows (ld % 8 == 0), the first F columns of every row are the features.  segment_reduce /
+    autograd.aggregate / aggregate_neighbors / SparseMatrix @ / the mean and sum GraphSAGE layers take it in place of a
+    float32 tensor and run tfgx_segment_reduce_h16 (include/tfgx_h16.h): a gathered row touches half the 128-byte lines,
+    and the result is, bit for bit, what the float32 route returns for .float().  Opt-in: a plain 16-bit torch.Tensor is
+    still widened by _lib.as_f32 and takes the float32 kernel."""
+
+    def __init__(self, table, F, source=None):
+        assert isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype in L.H16_DTYPES, \
+            "HalfRows: a 2-D torch.bfloat16 / torch.float16 tensor"
+        F = int(F)
+        ld = int(table.stride(0)) if table.shape[0] > 1 else int(table.shape[1])
+        if table.stride(1) != 1 or ld % 8 != 0 or ld < F or int(table.shape[1]) < min(ld, (F + 7) // 8 * 8) or table.data_ptr() % 16 != 0:
+            raise ValueError("HalfRows: rows must be 16-byte aligned and hold roundup8(F) elements (got shape {}, strides {}, "
+                             "F = {})".format(tuple(table.shape), tuple(table.stride()), F))
+        if int(table.shape[0]) > 0 and (table.storage_offset() + int(table.shape[0]) * ld) * 2 > table.untyped_storage().nbytes():
+            raise ValueError("HalfRows: every row, the last one included, must own its whole stride of {} elements".format(ld))
+        self.table, self.F, self.ld = table, F, ld
+        self.shape = (int(table.shape[0]), F)
+        self.dtype, self.device = table.dtype, table.device
+        self.source = source          # from_tensor: the caller's 16-bit tensor, which receives d/dx
+
+    @property
+    def requires_grad(self):
+        return self.source is not None and self.source.requires_grad
+
+    def float(self):
+        """The widened dense float32 [n, F] tensor (tfgx_rows_h16_to_f32: exact)."""
+        lib = L.require_gpu()
+        n, F = self.shape
+        out = torch.empty((n, F), dtype=torch.float32, device=self.device)
+        L.check(lib.tfgx_rows_h16_to_f32(L.ptr(self.table), self.ld, L.H16_DTYPES[self.dtype], n, F, L.ptr(out), max(F, 1),
+                                         L.stream_ptr()), "tfgx_rows_h16_to_f32")
+        return out
+
+    @staticmethod
+    def empty(n, F, dtype, device, ld=None):
+        """Uninitialised [n, F] table on the friendly stride (h16_friendly_ld) or on `ld`."""
+        ld = h16_friendly_ld(F) if ld is None else int(ld)
+        return HalfRows(torch.empty((int(n), ld), dtype=dtype, device=device), F)
+
+    @staticmethod
+    def from_dense(x, dtype=torch.bfloat16, ld=None, out=None):
+        """Quantise a float32 [n, F] tensor (tfgx_rows_f32_to_h16: round to nearest even) into `out` or a new table."""
+        lib = L.require_gpu()
+        if dtype not in L.H16_DTYPES:
+            raise TypeError("HalfRows: dtype must be torch.bfloat16 or torch.float16, got {}".format(dtype))
+        x, ldx = L.row_major_2d(L.as_f32(x).detach())
+        n, F = int(x.shape[0]), int(x.shape[1])
+        h = HalfRows.empty(n, F, dtype, x.device, ld) if out is None else out
+        assert h.shape == (n, F) and h.dtype == dtype
+        L.check(lib.tfgx_rows_f32_to_h16(L.ptr(x), ldx, n, F, L.ptr(h.table), h.ld, L.H16_DTYPES[dtype], L.stream_ptr()),
+                "tfgx_rows_f32_to_h16")
+        return h
+
+    @staticmethod
+    def from_tensor(t):
+        """A HalfRows over a 16-bit torch tensor [n, F] that may require grad: autograd.aggregate on it hands t the float32
+        gradient rounded to t.dtype.  The tensor itself is the table when its rows are 16-byte aligned, else its values are
+        copied onto the friendly stride."""
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in L.H16_DTYPES:
+            raise TypeError("HalfRows.from_tensor: a 2-D torch.bfloat16 / torch.float16 tensor")
+        dev = L.device()
+        d = t.detach()
+        if d.device != dev:
+            d = d.to(dev)
+        n, F = int(d.shape[0]), int(d.shape[1])
+        if not (d.is_contiguous() and F % 8 == 0 and d.data_ptr() % 16 == 0):
+            buf = torch.empty((n, h16_friendly_ld(F)), dtype=d.dtype, device=dev)
+            buf[:, :F].copy_(d)
+            d = buf
+        return HalfRows(d, F, source=t if t.requires_grad else None)
+
+
+def _h16_avg_lines(F, ld):
+    """Average number of 128-byte lines a row of roundup8(F) 16-bit elements touches when rows start ld elements apart."""
+    import math
+    row, stride = 2 * ((F + 7) // 8 * 8), 2 * ld
+    period = 128 // math.gcd(stride, 128)
+    return sum(((i * stride) % 128 + row - 1) // 128 + 1 for i in range(period)) / period
+
+
+def h16_friendly_ld(F):
+    """Row stride (in 16-bit elements) that keeps a gathered [*, F] row on the fewest 128-byte lines: gather_friendly_ld at 2
+    bytes per element, rows kept 16-byte aligned.  The Python statement of tfgx_h16_friendly_ld (tests hold the two equal)."""
+    F = int(F)
+    if F <= 0:
+        return 8
+    r8 = (F + 7) // 8 * 8
+    cands = [r8, (F + 31) // 32 * 32, (F + 63) // 64 * 64]
+    if F <= 64:
+        cands.append(max(8, 1 << (F - 1).bit_length()))
+    best = min(sorted(set(cands)), key=lambda ld: (round(_h16_avg_lines(F, ld), 6), ld))
+    if best >= 256 and (best & (best - 1)) == 0:
+        best += 64          # never a power-of-two row stride of 512 bytes or more: see pow2_row_stride
+    return best
+
+
+def _segment_reduce_h16(plan, h, op, w_csr, out, act, self_coef, bias, add_x, accumulate, mean_count, row_begin, row_end,
+                        rp_stride, col, n_dst, describe, wide_blocks, out_dtype):
+    """segment_reduce on a HalfRows: one launch of tfgx_segment_reduce_h16.  The verified / promoted-layout machinery is not
+    consulted; hub lists and the walk order come from the plan exactly as for float32."""
+    lib = L.require_gpu()
+    F = h.F
+    n_dst = plan.n_dst if n_dst is None else int(n_dst)
+    if out_dtype is not None and out_dtype not in L.H16_DTYPES and out_dtype != torch.float32:
+        raise TypeError("segment_reduce: out_dtype must be None, torch.float32, torch.bfloat16 or torch.float16")
+    half_out = out_dtype in L.H16_DTYPES
+    given = out is not None
+    if half_out:
+        if out is None:
+            out = HalfRows.empty(n_dst, F, out_dtype, h.device)
+        assert isinstance(out, HalfRows) and out.dtype == out_dtype and out.F == F, "out must be a HalfRows of out_dtype"
+        out_ptr, ldo = out.table.data_ptr(), out.ld
+    else:
+        if out is None:
+            out = torch.empty((n_dst, F), dtype=torch.float32, device=h.device)
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == h.device and out.dim() == 2
+                and int(out.shape[0]) >= n_dst and int(out.shape[1]) == F):
+            raise TypeError("segment_reduce on a HalfRows: out must be a float32 [n_dst, F] tensor on the table's device "
+                            "(or a HalfRows with out_dtype=)")
+        out2, ldo = L.row_major_2d(out)
+        assert out2 is out, "out must be row-major"
+        out_ptr = out.data_ptr()
+    a = L.ReduceArgs()
+    rb = plan.row_ptr if row_begin is None else row_begin
+    re = plan.row_ptr[1:] if row_end is None else row_end
+    a.row_begin, a.row_end, a.rp_stride = rb.data_ptr(), re.data_ptr(), rp_stride
+    a.col = (plan.col if col is None else col).data_ptr()
+    a.w = 0 if w_csr is None else w_csr.data_ptr()
+    a.n_dst = n_dst
+    a.x, a.ldx, a.F = h.table.data_ptr(), h.ld, F
+    a.out, a.ldo = out_ptr, ldo
+    a.op, a.act, a.accumulate = op, act, 1 if accumulate else 0
+    a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
+    a.bias = 0 if bias is None else bias.data_ptr()
+    if add_x is not None:
+        add_x, ld_add = L.row_major_2d(add_x)
+        a.add_x, a.ld_add = add_x.data_ptr(), ld_add
+    a.mean_count = 0 if mean_count is None else mean_count.data_ptr()
+    explicit = row_begin is not None or row_end is not None or col is not None
+    if not explicit and n_dst == plan.n_dst and USE_ROW_ORDER and F <= ROW_ORDER_MAX_F:
+        order = plan.row_order()
+        if order is not None:
+            a.row_order = order.data_ptr()
+    hub = plan.hub_info() if (not explicit and n_dst == plan.n_dst) else None
+    if hub is not None:
+        hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
+        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=h.device)
+        a.hub_threshold = plan.hub_threshold
+        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
+        a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
+        a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
+        a.hub_scratch = scratch.data_ptr()
+    a.wide_blocks = h16_wide_blocks_hint(explicit, hub is not None, plan.num_edges, n_dst) if wide_blocks is None else int(wide_blocks)
+    xdt = L.H16_DTYPES[h.dtype]
+    odt = L.H16_DTYPES[out_dtype] if half_out else L.DT_F32
+    if describe:
+        buf = ctypes.create_string_buffer(160)
+        L.check(lib.tfgx_segment_reduce_h16_describe(ctypes.byref(a), xdt, odt, buf, 160), "tfgx_segment_reduce_h16_describe")
+        return buf.value.decode()
+    L.check(lib.tfgx_segment_reduce_h16(ctypes.byref(a), xdt, odt, L.stream_ptr()), "tfgx_segment_reduce_h16")
+    _AGG_LAUNCHES[0] += 1
+    if given and not half_out:
+        written_by_kernel(out)
+    return out
+
+
+H16_WIDE_BLOCKS = True       # column blocks on wide 16-bit rows without hub lists: 14 % faster at F = 256 / 512 (profiles/h16_products.jsonl)
+
+
+def h16_wide_blocks_hint(explicit_spans, has_hub_lists, num_edges, n_rows):
+    """tfgx_reduce_args.wide_blocks of a 16-bit launch: +1 (column blocks of 128 elements on wide line-aligned rows) only when
+    H16_WIDE_BLOCKS is on and wide_blocks_hint would allow them for a float32 table; 0 otherwise (one burst per row)."""
+    if not H16_WIDE_BLOCKS or explicit_spans or has_hub_lists or num_edges < 32 * max(int(n_rows), 1):
+        return 0
+    return 1
+
+
 USE_ROW_ORDER = True      # degree-ordered row walk of the segment-reduce kernel on skewed plans (developer A/B switch)
 ROW_ORDER_MAX_F = 128     # ... applied up to this width (same-box A/B on R-MAT graphs, profiles/r04_ab_row_order.jsonl: see segment_reduce)
 
@@ -808,13 +988,22 @@ def wide_blocks_hint(explicit_spans, has_hub_lists, ldx, num_edges, n_rows):
 
 def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=None, bias=None, add_x=None,
                    accumulate=False, mean_count=None, row_begin=None, row_end=None, rp_stride=1, col=None,
-                   n_dst=None, describe=False, track=None, track_row_begin=None, wide_blocks=None):
+                   n_dst=None, describe=False, track=None, track_row_begin=None, wide_blocks=None, out_dtype=None):
     """One launch of tfgx_segment_reduce_f32 on `plan` (or on explicit row_begin/row_end/col views of it).
     `x` is a dense [n_src, F] tensor or a SplitRows.  describe=True launches nothing and returns the kernel symbol the
     dispatcher picks for these arguments (tfgx_segment_reduce_describe).  `track` (TFGX_MAX, training forward): int32
     [n_dst, F] that receives tie count << 16 | row-relative position of the first maximal edge (tfgx_reduce_args.track;
     see can_track); with accumulate=True the launch merges into the (out, track) earlier launches stored for earlier
-    sub-spans of the same rows (track_row_begin: the first position of the whole row)."""
+    sub-spans of the same rows (track_row_begin: the first position of the whole row).
+    `x` may also be a HalfRows (a 16-bit table): the launch is tfgx_segment_reduce_h16, float32 arithmetic, the float32
+    route's bits; out_dtype = torch.bfloat16 / torch.float16 then returns the result as a HalfRows (rounded as the last step)."""
+    if isinstance(x, HalfRows):
+        if track is not None or track_row_begin is not None:
+            raise L.TfgxError("tfgx_segment_reduce_h16: track: not supported on a 16-bit table (max aggregation is inference-only)")
+        return _segment_reduce_h16(plan, x, op, w_csr, out, act, self_coef, bias, add_x, accumulate, mean_count, row_begin,
+                                   row_end, rp_stride, col, n_dst, describe, wide_blocks, out_dtype)
+    if out_dtype not in (None, torch.float32):
+        raise TypeError("segment_reduce: out_dtype needs a HalfRows input")
     lib = L.require_gpu()
     split = x if isinstance(x, SplitRows) else None
     verified = None

@@ -52,7 +52,14 @@ class SparseMatrix(object):
 
     def matmul(self, h, num_or_size_splits=None):
         """out[r] = sum_{e: row_e = r} value_e * h[col_e]; duplicates sum. num_or_size_splits only bounds memory in
-        the reference (nn/conv/gcn.py:274-280) and never changes the result: nothing [E,F]-sized exists here."""
+        the reference (nn/conv/gcn.py:274-280) and never changes the result: nothing [E,F]-sized exists here.
+        h may be a plan.HalfRows (16-bit storage): float32 arithmetic and result on tfgx_segment_reduce_h16."""
+        from .plan import HalfRows
+        if isinstance(h, HalfRows):
+            from . import autograd as AG
+            if AG.needs_grad(h, self.value):
+                return AG.aggregate(self.plan, h, L.SUM, self.value[self.plan.perm.long()] if AG.needs_grad(self.value) else self.value_csr)
+            return segment_reduce(self.plan, h, L.SUM, w_csr=self.value_csr)
         h = L.as_f32(h)
         squeeze = h.dim() == 1
         if squeeze:
