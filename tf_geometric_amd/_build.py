@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libtfgx.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_misc.hip", "tfgx_backward.hip",
-           "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip"]
+           "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -26,11 +26,15 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     deps = [os.path.join(CSRC, "tfgx_common.h"), os.path.join(_HERE, "..", "include", "tfgx.h")]
     h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_h16.h")
+    fused_h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_fused_h16.h")
+    # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
+    own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
+                "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr, os.path.join(CSRC, "tfgx_mfma.h")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
-        if force or _newer(s, o) or any(_newer(d, o) for d in deps) or (src == "tfgx_reduce_h16.hip" and _newer(h16_hdr, o)):
+        if force or _newer(s, o) or any(_newer(d, o) for d in deps) or any(_newer(d, o) for d in own_deps.get(src, [])):
             jobs.append((s, o))
 
     def compile_one(job):

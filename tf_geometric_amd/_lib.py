@@ -257,6 +257,15 @@ H16_SIGNATURES = {
     "tfgx_h16_friendly_ld": (_I64, [_I64]),
 }
 
+# include/tfgx_fused_h16.h (the fused aggregate -> project launch over a 16-bit table): again its own header, version and table
+# — checked against that header by tests/test_fused_h16_abi.py.
+FUSED_H16_ABI_VERSION = 1
+FUSED_H16_SIGNATURES = {
+    "tfgx_fused_h16_version": (ctypes.c_int, []),
+    "tfgx_aggregate_gemm_h16": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _P, _I64, _P, _I32, _P, _I64, _I64, _P]),
+    "tfgx_aggregate_gemm_h16_describe": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I64, ctypes.c_char_p, ctypes.c_size_t]),
+}
+
 _lib = None
 
 
@@ -284,6 +293,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in FUSED_H16_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_fused_h16_version() != FUSED_H16_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_fused_h16 ABI {} but this package binds {} "
+                        "(include/tfgx_fused_h16.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_fused_h16_version(), FUSED_H16_ABI_VERSION))
     if lib.tfgx_h16_version() != H16_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_h16 ABI {} but this package binds {} (include/tfgx_h16.h): "
                         "rebuild with __graft_entry__.build()".format(LIB_PATH, lib.tfgx_h16_version(), H16_ABI_VERSION))

@@ -212,7 +212,10 @@ class _AggregateProject(torch.autograd.Function):
 
 def aggregate_project(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None, act=L.ACT_NONE, rows=None):
     """Differentiable act(reduce(plan, x) @ kernel + bias) on the fused launch, or None when it does not take the shape
-    (the caller then composes aggregate + linear).  rows: x's static layout (plan.static_rows) or None / x itself."""
+    (the caller then composes aggregate + linear).  rows: x's static layout (plan.static_rows) or None / x itself.
+    x may be a HalfRows (tfgx_aggregate_gemm_h16; rows is not consulted; trainable edge weights: NotImplementedError)."""
+    if isinstance(x, HalfRows):
+        return _aggregate_project_half(plan, x, op, kernel, w_csr, self_coef, bias, act)
     rows = rows if isinstance(rows, SplitRows) else None
     if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if rows is None else rows, kernel, op):
         return None
@@ -271,6 +274,8 @@ def sage_wide(plan, op, x, ks, kn, w_csr=None, bias=None, act=L.ACT_NONE, rows=N
     """Differentiable mean / sum GraphSAGE layer body (concat form, aggregation first) with the neighbour half on the fused
     launch, or None when it does not take the shape.  Edge weights are constants here (trainable ones take the un-fused route).
     rows: x's static layout (plan.static_rows) or None / x itself."""
+    if isinstance(x, HalfRows):
+        return _sage_wide_half(plan, op, x, ks, kn, w_csr, bias, act)
     rows = rows if isinstance(rows, SplitRows) else None
     if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if rows is None else rows, kn, op):
         return None
@@ -589,6 +594,116 @@ class _AggregateHalf(torch.autograd.Function):
         need_x, need_s = ctx.needs_input_grad[3], ctx.needs_input_grad[5] and self_coef is not None
         gx32, _, gs = _aggregate_backward(plan, ctx.mean, h.float() if need_s else None, w_csr, self_coef, g, need_x, False, need_s)
         return None, None, None, gx32 if need_x else None, None, gs, gb, None
+
+
+def _refuse_trainable_weights_half(w_csr):
+    if isinstance(w_csr, torch.Tensor) and w_csr.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("edge weights that require grad are not supported over a 16-bit table (the SDDMM is float32-only)")
+
+
+class _AggregateProjectHalf(torch.autograd.Function):
+    """_AggregateProject over a HalfRows: the forward is ONE launch of tfgx_aggregate_gemm_h16 (the float32 route's bits, the
+    float32 aggregate written beside it when the kernel wants a gradient), the backward the existing float32 kernels; d/dx goes,
+    in float32, to the table's gradient sink (_HalfGradSink), as in _AggregateHalf."""
+
+    @staticmethod
+    def forward(ctx, plan, mean, h, proxy, w_csr, self_coef, kernel, bias, act):
+        agg = torch.empty((plan.n_dst, h.F), dtype=torch.float32, device=h.device) if ctx.needs_input_grad[6] else None
+        out = aggregate_gemm(plan, h, L.MEAN if mean else L.SUM, kernel.detach(), w_csr=w_csr,
+                             self_coef=None if self_coef is None else self_coef.detach(),
+                             bias=None if bias is None else bias.detach(), act=act, agg_out=agg, training=True)
+        if out is None:
+            raise L.TfgxError("_AggregateProjectHalf: the fused launch declined (ask plan.aggregate_gemm_applies first)")
+        ctx.plan, ctx.mean, ctx.act, ctx.h = plan, mean, act, h
+        ctx.save_for_backward(w_csr, self_coef, kernel, bias, agg, out if act == L.ACT_RELU else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w_csr, self_coef, kernel, bias, agg, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_b = bias is not None and need[7]
+        need_x, need_s = need[3], need[5] and self_coef is not None
+        gated = (ctx.act == L.ACT_RELU and agg is not None and (need[6] or want_b) and not (need_x or need_s)
+                 and GATED_AGGREGATE_PROJECT)
+        if not gated:
+            g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
+        gk = gb = None
+        if need[6] or want_b:
+            if agg is not None:
+                gk, gb = gemm_tn(agg, g.contiguous() if gated else g, want_bias=want_b, gate=out if gated else None)
+                if not need[6]:
+                    gk = None
+            else:
+                gb = column_sums(g)
+        gx = gs = None
+        if need_x or need_s:
+            g_agg = gemm_bias_act(g, transpose(kernel.detach()))          # d/d(aggregate) = g @ kernel^T
+            gx, _, gs = _aggregate_backward(ctx.plan, ctx.mean, ctx.h.float() if need_s else None, w_csr, self_coef, g_agg,
+                                            need_x, False, need_s)
+        return None, None, None, gx if need_x else None, None, gs, gk, gb, None
+
+
+def _aggregate_project_half(plan, h, op, kernel, w_csr, self_coef, bias, act):
+    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(h, kernel, op):
+        return None
+    _refuse_trainable_weights_half(w_csr)
+    return _AggregateProjectHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), None if w_csr is None else w_csr.detach(),
+                                       self_coef, L.as_f32(kernel), None if bias is None else L.as_f32(bias), act)
+
+
+class _SageWideHalf(torch.autograd.Function):
+    """_SageWide over a HalfRows: the neighbour half is ONE launch of tfgx_aggregate_gemm_h16 straight into its half of h, the
+    self half the float32 GEMM on the widened table xw = widen(h).  d/dx of the neighbour half goes to the table's gradient
+    sink, that of the self half to xw (which leads to the same sink): summed in float32, rounded once."""
+
+    @staticmethod
+    def forward(ctx, plan, mean, hrows, proxy, xw, ks, kn, w_csr, bias, act):
+        n, F, na, nb = hrows.shape[0], hrows.F, int(ks.shape[1]), int(kn.shape[1])
+        h = torch.empty((n, na + nb), dtype=torch.float32, device=hrows.device)
+        bd = None if bias is None else bias.detach().contiguous()
+        agg = torch.empty((n, F), dtype=torch.float32, device=hrows.device) if ctx.needs_input_grad[6] else None
+        got = aggregate_gemm(plan, hrows, L.MEAN if mean else L.SUM, kn.detach(), w_csr=w_csr,
+                             bias=None if bd is None else bd[na:].contiguous(), act=act, out=h[:, na:], agg_out=agg, training=True)
+        if got is None:
+            raise L.TfgxError("_SageWideHalf: the fused launch declined (ask plan.aggregate_gemm_applies first)")
+        gemm_bias_act(xw.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
+        ctx.plan, ctx.mean, ctx.act, ctx.na = plan, mean, act, na
+        ctx.save_for_backward(xw, ks, kn, w_csr, bias, agg, h if act == L.ACT_RELU else None)
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        xw, ks, kn, w_csr, bias, agg, h = ctx.saved_tensors
+        plan, na, need = ctx.plan, ctx.na, ctx.needs_input_grad
+        want_b = bias is not None and need[8]
+        need_x = need[3] or need[4]
+        gated = ctx.act == L.ACT_RELU and not need_x and agg is not None and GATED_AGGREGATE_PROJECT
+        g = g.contiguous() if (gated or ctx.act != L.ACT_RELU) else relu_backward(g, h)
+        gs, gn = g[:, :na], g[:, na:]
+        gxw, gks, gba = _linear_grads(xw, ks, gs, need_x, need[5], want_b, gate=h[:, :na] if gated else None)
+        gkn = gbb = None
+        if need[6] or want_b:
+            if agg is not None:
+                gkn, gbb = gemm_tn(agg, gn, want_bias=want_b, gate=h[:, na:] if gated else None)
+                if not need[6]:
+                    gkn = None
+            else:
+                gbb = column_sums(gn)
+        gx = None
+        if need_x:
+            g_agg = gemm_bias_act(gn, transpose(kn.detach()))
+            gx, _, _ = _aggregate_backward(plan, ctx.mean, None, w_csr, None, g_agg, True, False, False)
+        gb = torch.cat([gba, gbb]) if want_b else None
+        return None, None, None, gx if need[3] else None, gxw if need[4] else None, gks, gkn, None, gb, None
+
+
+def _sage_wide_half(plan, op, h, ks, kn, w_csr, bias, act):
+    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(h, kn, op):
+        return None
+    _refuse_trainable_weights_half(w_csr)
+    return _SageWideHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), widen(h), L.as_f32(ks), L.as_f32(kn),
+                               None if w_csr is None else w_csr.detach(), None if bias is None else L.as_f32(bias), act)
 
 
 def _aggregate_half(plan, h, op, w_csr, self_coef, bias, act, rows=None, max_passes=None):

@@ -86,7 +86,7 @@ class GCN(Layer):
                         cache[CACHE_KEY_PLAN] = sparse_adj.plan
                     cache[key] = sparse_adj
         from ...plan import HalfRows
-        x_in = x if (isinstance(x, (SparseMatrix, HalfRows)) or getattr(x, "is_sparse", False)) else as_f32(x)   # sparse x: :269-270; a HalfRows is refused by gcn()
+        x_in = x if (isinstance(x, (SparseMatrix, HalfRows)) or getattr(x, "is_sparse", False)) else as_f32(x)   # sparse x: :269-270; a HalfRows: gcn() takes it when the layer aggregates x itself
         return gcn(x_in, sparse_adj, self.kernel, self.bias, activation=self.activation,
                    norm=self.norm, add_self_loop=self.add_self_loop, sym=self.sym, renorm=self.renorm,
                    improved=self.improved, edge_drop_rate=self.edge_drop_rate,

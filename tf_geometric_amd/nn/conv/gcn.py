@@ -162,12 +162,38 @@ def gcn_mapper(repeated_x, neighbor_x, edge_weight=None):
     return _m(repeated_x, neighbor_x, edge_weight)
 
 
+def _gcn_half(h, normed, kernel, bias, activation):
+    """gcn() on a HalfRows (16-bit table) in its aggregation-first form, act((A_hat x) @ kernel + bias) or act(A_hat x + bias):
+    the fused launch on the 16-bit table (tfgx_aggregate_gemm_h16), or tfgx_segment_reduce_h16 followed by the float32 GEMM
+    when it declines.  The static layouts (static_rows / static_aggregate: promotion, memo) are not consulted."""
+    act, post = _resolve_act(activation)
+    plan, w_csr, sc = normed.plan, normed.w_csr, normed.self_coef
+    if AG.needs_grad(h, kernel, bias):
+        bias_t = None if bias is None else L.as_f32(bias)
+        if kernel is None:
+            out = AG.aggregate(plan, h, L.SUM, w_csr, sc, bias=bias_t, act=act)
+        else:
+            out = AG.aggregate_project(plan, h, L.SUM, kernel, w_csr, sc, bias_t, act)
+            if out is None:
+                out = AG.linear(AG.aggregate(plan, h, L.SUM, w_csr, sc), kernel, bias_t, act)
+        return post(out) if post is not None else out
+    bias_t = None if bias is None else L.as_f32(bias).contiguous()
+    if kernel is None:
+        out = segment_reduce(plan, h, L.SUM, w_csr=w_csr, self_coef=sc, bias=bias_t, act=act)
+    else:
+        out = aggregate_gemm(plan, h, L.SUM, kernel, w_csr=w_csr, self_coef=sc, bias=bias_t, act=act)
+        if out is None:
+            out = gemm_bias_act(segment_reduce(plan, h, L.SUM, w_csr=w_csr, self_coef=sc), kernel, bias=bias_t, act=act)
+    return post(out) if post is not None else out
+
+
 def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self_loop=True, sym=True,
         renorm=True, improved=False, edge_drop_rate=0.0, num_or_size_splits=None, training=False, cache=None):
     """
     Functional GCN (reference: gcn.py:225-290; same arguments).
 
-    :param x: [num_nodes, num_features]; dense, or sparse (this package's SparseMatrix / a torch sparse COO tensor)
+    :param x: [num_nodes, num_features]; dense, or sparse (this package's SparseMatrix / a torch sparse COO tensor), or a
+        plan.HalfRows (16-bit table) when the layer aggregates x itself: kernel is None or units > num_features
     :param sparse_adj: SparseMatrix adjacency
     :param kernel: [num_features, num_output_features] or None (skip the GEMM, :266-267)
     :param num_or_size_splits: accepted for compatibility; it bounds memory in the reference and never changes
@@ -177,9 +203,13 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     L.require_gpu()
     from ...plan import HalfRows
     if isinstance(x, HalfRows):
-        raise TypeError("gcn multiplies x by its kernel before aggregating when units < num_features (and fuses the GEMM into "
-                        "the aggregation otherwise): a HalfRows (16-bit table) is taken by the aggregation kernels only — "
-                        "16-bit GEMM operands are out of scope; pass x.float()")
+        if kernel is not None and not x.F < int(kernel.shape[1]):
+            raise TypeError("gcn multiplies x by its kernel before aggregating when units <= num_features: a HalfRows (16-bit "
+                            "table) is taken by the aggregation kernels only (kernel=None, or units > num_features, where the "
+                            "layer aggregates x itself) — 16-bit GEMM operands are out of scope; pass x.float()")
+        normed = gcn_norm_adj(sparse_adj, norm=norm, add_self_loop=add_self_loop, sym=sym, renorm=renorm,
+                              improved=improved, cache=cache)
+        return _gcn_half(x, normed.dropout(edge_drop_rate, training=training), kernel, bias, activation)
     xs = sparse_features(x)
     if xs is not None:
         # sparse node features (one-hot / bag-of-words rows; tf.sparse.sparse_dense_matmul, :269-270):

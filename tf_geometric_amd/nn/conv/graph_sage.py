@@ -123,6 +123,33 @@ def _concat_fused_training(x, edge_index, edge_weight, ws, wn, bias, activation,
     return h
 
 
+def _concat_fused_half(x, plan, w_csr, ws, wn, bias, activation, normalize, op):
+    """_concat_fused / _concat_fused_training for a HalfRows x: the neighbour half on tfgx_aggregate_gemm_h16, the self half the
+    float32 GEMM on the widened table.  None when the fused launch does not take the call."""
+    act, post = _resolve_act(activation)
+    if AG.needs_grad(x, ws, wn, bias):
+        h = AG.sage_wide(plan, op, x, ws, wn, w_csr, bias, act)
+        if h is None:
+            return None
+        if post is not None:
+            h = post(h)
+        if normalize:
+            h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
+        return h
+    n, ku_x, ku_n = int(x.shape[0]), int(ws.shape[1]), int(wn.shape[1])
+    bias_t = None if bias is None else L.as_f32(bias).contiguous()
+    h = torch.empty((n, ku_x + ku_n), dtype=torch.float32, device=x.device)
+    if aggregate_gemm(plan, x, op, wn, w_csr=w_csr, bias=None if bias_t is None else bias_t[ku_x:].contiguous(), act=act,
+                      out=h[:, ku_x:]) is None:
+        return None
+    gemm_bias_act(x.float(), ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
+    if post is not None:
+        h = post(h)
+    if normalize:
+        h = l2_normalize_rows_(h.contiguous())
+    return h
+
+
 def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel, bias, activation, concat, normalize,
                         op, cache):
     """mean / sum GraphSAGE (reference :9-115).  Both reducers are linear, so
@@ -130,14 +157,22 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
     input (hidden layers: 256 -> units/2) the GEMM runs first and the gather moves 4*ku instead of 4*F bytes per edge —
     the same move as GCN's narrow-side aggregation; bias and activation ride in the aggregation's
     epilogue and the result lands directly in its half of the output.  Same value up to fp32 re-association.
-    A HalfRows x (16-bit storage): the neighbour half aggregates on tfgx_segment_reduce_h16 into float32, the projections run
-    on the float32 GEMM, the self half reads x.float()."""
+    A HalfRows x (16-bit storage): aggregation first with concat takes the fused launch on the 16-bit table
+    (tfgx_aggregate_gemm_h16); otherwise the neighbour half aggregates on tfgx_segment_reduce_h16 into float32 and the
+    projections run on the float32 GEMM.  The self half reads x.float()."""
     if isinstance(x, HalfRows):
         n = int(x.shape[0])
         plan = CsrPlan.from_cache(edge_index, n, n, cache)
         w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
+        ws, wn = L.as_f32(self_kernel), L.as_f32(neighbor_kernel)
+        if not int(wn.shape[1]) < x.F and concat and not AG.needs_grad(edge_weight):
+            # aggregation first, concat: the neighbour half is ONE launch on the 16-bit table (tfgx_aggregate_gemm_h16) straight
+            # into its half of the output — inference and training as on the float32 path; None: the launch declines
+            h = _concat_fused_half(x, plan, w_csr, ws, wn, bias, activation, normalize, op)
+            if h is not None:
+                return h
         reduced = AG.aggregate(plan, x, op, w_csr) if AG.needs_grad(x, edge_weight) else segment_reduce(plan, x, op, w_csr=w_csr)
-        return _combine(L.as_f32(self_kernel), AG.widen(x), L.as_f32(neighbor_kernel), reduced, bias, activation, concat, normalize)
+        return _combine(ws, AG.widen(x), wn, reduced, bias, activation, concat, normalize)
     x = L.as_f32(x)
     wn = L.as_f32(neighbor_kernel)
     ws = L.as_f32(self_kernel)

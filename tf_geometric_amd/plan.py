@@ -1107,6 +1107,7 @@ TFGX_FUSE_WIDE = False          # developer A/B switch: True = the fused launch 
 
 
 FUSED_STATS = {"launches": 0, "with_side_output": 0}      # diagnostics (tests assert the route taken)
+FUSED_H16_STATS = {"launches": 0}     # of those, the launches over a 16-bit table (tfgx_aggregate_gemm_h16)
 
 
 def aggregate_gemm_applies(x, kernel, op=L.SUM):
@@ -1115,20 +1116,28 @@ def aggregate_gemm_applies(x, kernel, op=L.SUM):
     if not FUSE_AGGREGATE_GEMM or op not in (L.SUM, L.MEAN) or kernel is None:
         return False
     lib = L.require_gpu()
+    if isinstance(x, HalfRows):      # a 16-bit table: tfgx_aggregate_gemm_h16 (HalfRows keeps its rows 16-byte aligned)
+        return bool(int(kernel.shape[0]) == x.F and lib.tfgx_aggregate_gemm_fits(x.F, int(kernel.shape[1])))
     x2, ldx = L.row_major_2d(x.main if isinstance(x, SplitRows) else x)
     F, N = (x.shape[1] if isinstance(x, SplitRows) else int(x2.shape[1])), int(kernel.shape[1])
     return bool(int(kernel.shape[0]) == F and lib.tfgx_aggregate_gemm_fits(F, N) and ldx % 4 == 0
                 and x2.data_ptr() % 16 == 0)
 
 
-def aggregate_gemm(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None, act=L.ACT_NONE, out=None, agg_out=None):
+def aggregate_gemm(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None, act=L.ACT_NONE, out=None, agg_out=None,
+                   training=False):
     """act(segment_reduce(plan, x, op, w_csr, self_coef) @ kernel + bias) in ONE launch (tfgx_aggregate_gemm_f32: the
     aggregate goes registers -> LDS -> MFMA and is never read back from HBM), or None when the fused kernel does not take
     this call (shape outside tfgx_aggregate_gemm_fits, unaligned rows) — the caller then runs the two launches.
     agg_out: optional dense [n_dst, F] tensor that ALSO receives the aggregate itself (the training forward: the weight
-    gradient needs it)."""
+    gradient needs it).
+    x may be a HalfRows (a 16-bit table): the launch is tfgx_aggregate_gemm_h16 — float32 arithmetic, float32 C and side output,
+    the bits of this call on x.float() with the same plan.  training=True (the autograd routes over a HalfRows): the measured
+    inference-only declining rule of _fused_h16_declines is not applied."""
     if not FUSE_AGGREGATE_GEMM or op not in (L.SUM, L.MEAN):
         return None
+    if isinstance(x, HalfRows):
+        return _aggregate_gemm_h16(plan, x, op, kernel, w_csr, self_coef, bias, act, out, agg_out, training)
     lib = L.require_gpu()
     split = x if isinstance(x, SplitRows) else None       # static feature layout: main / tail / per-edge tail (as segment_reduce)
     x2, ldx = L.row_major_2d(split.main if split is not None else x)
@@ -1187,6 +1196,82 @@ def aggregate_gemm(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None, a
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
     L.check(lib.tfgx_aggregate_gemm_f32(ctypes.byref(a), L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out), ldc, N,
                                         L.stream_ptr()), "tfgx_aggregate_gemm_f32")
+    if given:
+        written_by_kernel(out)
+    written_by_kernel(agg_out)
+    return out
+
+
+FUSED_H16_DECLINE_HUB_INFERENCE = True      # developer A/B switch (tools/bench_fused_half.py sets it False): see _fused_h16_declines
+
+
+def _fused_h16_declines(plan, h, training):
+    """Does aggregate_gemm leave this HalfRows call to the two launches (tfgx_segment_reduce_h16 + float32 GEMM)?  Decided from
+    tools/bench_fused_half.py (profiles/fused_h16_products.jsonl; products shape, one process, interleaved, median ms, two
+    launches against fused, run-to-run spread about 1 %):
+      * uniform graph (no hub lists): fused ahead everywhere — GCN 100 -> 256 inference 5.72 vs 5.04, training 8.78 vs 6.90;
+        mean GraphSAGE 6.29 vs 5.82 / 9.69 vs 7.96; 128 -> 256: 6.09 vs 5.50, 9.45 vs 8.04, 6.55 vs 5.93, 10.11 vs 8.59.
+      * R-MAT graph (97 k hub rows, chunk partials by a launch of their own), INFERENCE: fused BEHIND — GCN 100 -> 256 6.35 vs
+        6.66, mean GraphSAGE 6.85 vs 7.16; 128 -> 256: 6.69 vs 7.36, 6.94 vs 7.31.  Declined here, for tables past the 256 MB
+        Infinity Cache (the measured regime: a 627 MB table; smaller tables were not measured and keep the one launch).
+      * R-MAT, TRAINING forward + backward (the side output saves the aggregate's read-back): fused ahead — 9.30 vs 8.52,
+        10.10 vs 9.40; 128 -> 256: 9.94 vs 9.68, 10.54 vs 10.00.  Kept.
+    The float32 rule for F = 128 on large dense tables (aggregate_gemm above) does not carry over: it is the float32 producers
+    against the float32 column-block gather; at F = 128 on the uniform graph this launch is ahead (6.09 vs 5.50)."""
+    return bool(FUSED_H16_DECLINE_HUB_INFERENCE and not training and plan.hub_info() is not None
+                and 2 * h.shape[0] * h.ld > (256 << 20))
+
+
+def _aggregate_gemm_h16(plan, h, op, kernel, w_csr, self_coef, bias, act, out, agg_out, training=False):
+    """aggregate_gemm on a HalfRows: one launch of tfgx_aggregate_gemm_h16 (include/tfgx_fused_h16.h), or None when the shape
+    is outside tfgx_aggregate_gemm_fits or the measured rule of _fused_h16_declines says so (never for a training forward:
+    training=True, or an agg_out).  Hub lists, the walk order and hub_order_slot come from the plan exactly as for
+    float32; the split / static layouts and relaid_for_gather do not apply to a 16-bit table."""
+    lib = L.require_gpu()
+    k2, ldb = L.row_major_2d(L.as_f32(kernel))
+    F, N = h.F, int(k2.shape[1])
+    if int(k2.shape[0]) != F or not lib.tfgx_aggregate_gemm_fits(F, N):
+        return None
+    if _fused_h16_declines(plan, h, training or agg_out is not None):
+        return None
+    hub = plan.hub_info()
+    order = plan.row_order()
+    n_dst = plan.n_dst
+    given = out is not None
+    if out is None:
+        out = torch.empty((n_dst, N), dtype=torch.float32, device=h.device)
+    _, ldc = L.row_major_2d(out)
+    a = L.ReduceArgs()
+    a.row_begin, a.row_end, a.rp_stride = plan.row_ptr.data_ptr(), plan.row_ptr[1:].data_ptr(), 1
+    a.col = plan.col.data_ptr()
+    a.w = 0 if w_csr is None else w_csr.data_ptr()
+    a.n_dst, a.x, a.ldx, a.F = n_dst, h.table.data_ptr(), h.ld, F
+    a.op = op
+    a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
+    if order is not None:
+        a.row_order = order.data_ptr()
+    if hub is not None:
+        hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
+        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=h.device)
+        a.hub_threshold = plan.hub_threshold
+        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
+        a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
+        a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
+        a.hub_scratch = scratch.data_ptr()
+        slot = plan.hub_order_slot()
+        if slot is not None:
+            a.hub_order_slot = slot.data_ptr()
+    if agg_out is not None:
+        ao, ldo = L.row_major_2d(agg_out)
+        assert ao is agg_out and tuple(agg_out.shape) == (n_dst, F) and ldo % 4 == 0 and agg_out.data_ptr() % 16 == 0
+        a.out, a.ldo = agg_out.data_ptr(), ldo
+        FUSED_STATS["with_side_output"] += 1
+    FUSED_STATS["launches"] += 1
+    FUSED_H16_STATS["launches"] += 1
+    _AGG_LAUNCHES[0] += 1
+    bias_t = None if bias is None else L.as_f32(bias).contiguous()
+    L.check(lib.tfgx_aggregate_gemm_h16(ctypes.byref(a), L.H16_DTYPES[h.dtype], L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out),
+                                        ldc, N, L.stream_ptr()), "tfgx_aggregate_gemm_h16")
     if given:
         written_by_kernel(out)
     written_by_kernel(agg_out)
