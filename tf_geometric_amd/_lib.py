@@ -266,6 +266,26 @@ FUSED_H16_SIGNATURES = {
     "tfgx_aggregate_gemm_h16_describe": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I64, ctypes.c_char_p, ctypes.c_size_t]),
 }
 
+
+
+class DropEdgePlan(ctypes.Structure):
+    """struct tfgx_drop_edge_plan (include/tfgx_dropedge.h)."""
+    _fields_ = [("parent_row_ptr", ctypes.c_void_p), ("parent_col", ctypes.c_void_p), ("parent_perm", ctypes.c_void_p),
+                ("out_row_ptr", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_perm", ctypes.c_void_p)]
+
+
+# include/tfgx_dropedge.h (DropEdge: edge dropout with sort-free plans): its own header, version and table — checked against
+# that header by tests/test_drop_edge_abi.py.
+DROPEDGE_ABI_VERSION = 1
+DROPEDGE_SIGNATURES = {
+    "tfgx_dropedge_version": (ctypes.c_int, []),
+    "tfgx_drop_edge_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I32, _I32]),
+    "tfgx_drop_edge_count": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F32, ctypes.c_uint64, _I32, ctypes.POINTER(ctypes.c_int64),
+                                            _P, _SZ, _P]),
+    "tfgx_drop_edge_emit": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _F32, ctypes.c_uint64, _I32, _I64, _P, _P, _P,
+                                           ctypes.POINTER(DropEdgePlan), ctypes.POINTER(DropEdgePlan), _P, _SZ, _P]),
+}
+
 _lib = None
 
 
@@ -297,6 +317,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in DROPEDGE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_dropedge_version() != DROPEDGE_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_dropedge ABI {} but this package binds {} "
+                        "(include/tfgx_dropedge.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_dropedge_version(), DROPEDGE_ABI_VERSION))
     if lib.tfgx_fused_h16_version() != FUSED_H16_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_fused_h16 ABI {} but this package binds {} "
                         "(include/tfgx_fused_h16.h): rebuild with __graft_entry__.build()".format(

@@ -6,3 +6,4 @@ from .conv.graph_sage import MeanGraphSage, SumGraphSage, GCNGraphSage, MeanPool
 from .kernel.map_reduce import MapReduceGNN
 from .conv.propagation import GIN, SGC, TAGCN, APPNP, SSGC, ChebyNet, LEConv
 from .pool import CommonPool, MeanPool, SumPool, MaxPool, MinPool, SAGPool, SortPool
+from .sampling import DropEdge

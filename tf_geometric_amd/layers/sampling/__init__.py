@@ -1,0 +1,2 @@
+# coding=utf-8
+from .drop_edge import DropEdge
