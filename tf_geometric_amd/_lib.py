@@ -286,6 +286,19 @@ DROPEDGE_SIGNATURES = {
                                            ctypes.POINTER(DropEdgePlan), ctypes.POINTER(DropEdgePlan), _P, _SZ, _P]),
 }
 
+# include/tfgx_linkpred.h (link prediction: the per-edge decoder and the negative samplers): its own header, version and
+# table — checked against that header by tests/test_linkpred_abi.py.
+LINKPRED_ABI_VERSION = 1
+NEGATIVE_BAD_START = -(1 << 31)     # TFGX_NEGATIVE_BAD_START as the int32 the device word is read as
+_U64, _U32 = ctypes.c_uint64, ctypes.c_uint32
+LINKPRED_SIGNATURES = {
+    "tfgx_linkpred_version": (ctypes.c_int, []),
+    "tfgx_edge_dot_f32": (ctypes.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "tfgx_negative_draw": (None, [_U64, _U64, _U32, _I64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "tfgx_negative_sample_pairs": (ctypes.c_int, [_I64, _I64, _P, _P, _I32, _U64, _U64, _I32, _P, _P, _P, _P]),
+    "tfgx_negative_sample_from": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _U64, _U64, _I32, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -321,6 +334,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in LINKPRED_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_linkpred_version() != LINKPRED_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_linkpred ABI {} but this package binds {} "
+                        "(include/tfgx_linkpred.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_linkpred_version(), LINKPRED_ABI_VERSION))
     if lib.tfgx_dropedge_version() != DROPEDGE_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_dropedge ABI {} but this package binds {} "
                         "(include/tfgx_dropedge.h): rebuild with __graft_entry__.build()".format(

@@ -1261,3 +1261,49 @@ class _GatherEdges(torch.autograd.Function):
 
 def gather_edges(w, edge_id):
     return _GatherEdges.apply(L.as_f32(w).reshape(-1), edge_id)
+
+
+def edge_dot_forward(z, z_other, row, col, bad_flag=None):
+    """One tfgx_edge_dot_f32 launch (include/tfgx_linkpred.h): out[e] = <z[row[e]], z_other[col[e]]>, no plan."""
+    lib = L.require_gpu()
+    a, lda = L.row_major_2d(z)
+    b, ldb = (a, lda) if z_other is z else L.row_major_2d(z_other)
+    E = int(row.shape[0])
+    out = torch.empty(E, dtype=torch.float32, device=a.device)
+    L.check(lib.tfgx_edge_dot_f32(L.ptr(row), L.ptr(col), E, L.ptr(a), lda, int(a.shape[0]), L.ptr(b), ldb, int(b.shape[0]),
+                                  int(a.shape[1]), L.ptr(out), L.ptr(bad_flag), L.stream_ptr()), "tfgx_edge_dot_f32")
+    return out
+
+
+class _EdgeDot(torch.autograd.Function):
+    """logit[e] = <z[row[e]], z_other[col[e]]> (the link-prediction decoder).  Backward on the aggregation kernels:
+    dz[i] = sum_{e: row[e] = i} g[e] * z_other[col[e]] is a weighted segment sum on the list's plan, d z_other the same on
+    the transposed plan; with a shared table (z_other is None) the two are added.  Fixed reduction order: bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, plan, z, z_other, row, col):
+        ctx.plan = plan
+        zd = z.detach()
+        ctx.save_for_backward(z, z_other)
+        return edge_dot_forward(zd, zd if z_other is None else z_other.detach(), row, col)
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.plan
+        z, z_other = ctx.saved_tensors
+        shared = z_other is None
+        other = z if shared else z_other
+        g = g.contiguous()
+        gz = go = None
+        if ctx.needs_input_grad[1]:
+            gz = segment_reduce(plan, other.detach(), L.SUM, w_csr=plan.edge_attr_to_csr(g))
+        if shared or ctx.needs_input_grad[2]:
+            pt = plan.transposed()
+            go = segment_reduce(pt, z.detach(), L.SUM, w_csr=pt.edge_attr_to_csr(g))
+        if shared:
+            return None, (gz + go) if gz is not None else None, None, None, None
+        return None, gz, go if ctx.needs_input_grad[2] else None, None, None
+
+
+def edge_dot(plan, z, z_other, row, col):
+    return _EdgeDot.apply(plan, z, z_other, row, col)

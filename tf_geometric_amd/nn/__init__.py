@@ -11,3 +11,4 @@ from .conv.graph_sage import (mean_graph_sage, sum_graph_sage, gcn_graph_sage, m
 from .conv.propagation import gin, sgc, tagcn, appnp, ssgc, chebynet, le_conv, chebynet_norm_edge
 from .pool import mean_pool, sum_pool, max_pool, min_pool, topk_pool, sag_pool, sort_pool
 from .sampling import drop_edge
+from .link import edge_dot

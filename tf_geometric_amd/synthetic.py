@@ -120,3 +120,23 @@ WORKLOADS = {
     "cora": (2708, 10556, 1433),             # Cora-shaped (configs[0])
     "tiny": (20000, 400000, 100),            # plumbing check
 }
+
+
+def planted_partition_graph(num_nodes, classes=6, degree=12, features=32, seed=0):
+    """A graph with community structure for the link-prediction example: 80 % of a node's edges go to nodes of its own
+    class, both directions are emitted [all (a,b) | all (b,a)], features are noise plus a class direction.
+    Returns (x float32 [N, features], edge_index int32 [2, ~N * degree], y int64 [N])."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = int(num_nodes)
+    y = rng.integers(0, classes, n)
+    order = np.argsort(y, kind="stable")
+    pos = np.empty(n, np.int64)
+    pos[order] = np.arange(n)
+    a = rng.integers(0, n, n * degree // 2)
+    near = order[np.clip(pos[a] + rng.integers(-30, 31, a.shape[0]), 0, n - 1)]
+    b = np.where(rng.random(a.shape[0]) < 0.8, near, rng.integers(0, n, a.shape[0]))
+    a, b = a[a != b], b[a != b]
+    edge_index = np.stack([np.concatenate([a, b]), np.concatenate([b, a])]).astype(np.int32)
+    centers = rng.standard_normal((classes, features)).astype(np.float32)
+    x = (rng.standard_normal((n, features)) + centers[y]).astype(np.float32)
+    return x, edge_index, y.astype(np.int64)

@@ -6,6 +6,8 @@ import torch
 
 from .. import _lib as L
 from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
+from .link import (negative_sampling, negative_sampling_with_start_node, edge_train_test_split, extract_unique_edge,
+                   convert_edge_index_to_edge_hash, convert_edge_hash_to_edge_index, sorted_adjacency)
 
 
 def add_self_loop_edge(edge_index, num_nodes, edge_weight=None, fill_weight=1.0):
