@@ -299,6 +299,19 @@ LINKPRED_SIGNATURES = {
     "tfgx_negative_sample_from": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _U64, _U64, _I32, _P, _P, _P]),
 }
 
+# include/tfgx_lstm.h (the LSTM GraphSAGE aggregator: fused gather -> recurrence and its backward through time): its own
+# header, version and table — checked against that header by tests/test_lstm_abi.py.
+LSTM_ABI_VERSION = 1
+LSTM_MAX_UNITS = 256
+LSTM_SIGNATURES = {
+    "tfgx_lstm_version": (ctypes.c_int, []),
+    "tfgx_lstm_recurrent_kernel_resident": (ctypes.c_int, [_I64, _I32]),
+    "tfgx_lstm_aggregate_saved_bytes": (_SZ, [_I64, _I64, _I64]),
+    "tfgx_lstm_aggregate_tiles": (_I64, [_I64]),
+    "tfgx_lstm_aggregate_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _SZ, _P, _P]),
+    "tfgx_lstm_aggregate_backward_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -338,6 +351,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in LSTM_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_lstm_version() != LSTM_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_lstm ABI {} but this package binds {} "
+                        "(include/tfgx_lstm.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_lstm_version(), LSTM_ABI_VERSION))
     if lib.tfgx_linkpred_version() != LINKPRED_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_linkpred ABI {} but this package binds {} "
                         "(include/tfgx_linkpred.h): rebuild with __graft_entry__.build()".format(

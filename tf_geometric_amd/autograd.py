@@ -1307,3 +1307,95 @@ class _EdgeDot(torch.autograd.Function):
 
 def edge_dot(plan, z, z_other, row, col):
     return _EdgeDot.apply(plan, z, z_other, row, col)
+
+
+# ---- the LSTM aggregator of GraphSAGE (include/tfgx_lstm.h)
+def lstm_max_degree(plan):
+    """T of the LSTM aggregator: the plan's longest row, read once (the layer's only host synchronisation) and kept on the plan."""
+    if getattr(plan, "_max_degree", None) is None:
+        plan._max_degree = int(plan.in_degree().max().item()) if (plan.n_dst > 0 and plan.num_edges > 0) else 0
+    return plan._max_degree
+
+
+def _lstm_step_plan(plan, T):
+    """The plan of dP[j] = sum over (i, t) with neighbour j of d_gates[i * T + t]: the transposed plan's rows with the column
+    of an edge replaced by i * T + its position t inside row i of `plan`.  Derived once per (plan, T), kept on the plan."""
+    memo = getattr(plan, "_lstm_step_plans", None)
+    if memo is None:
+        memo = plan._lstm_step_plans = {}
+    if T not in memo:
+        if plan.n_dst * T >= (1 << 31):
+            raise L.TfgxError("lstm_aggregate: n_dst * T = {} does not fit the int32 columns of a plan".format(plan.n_dst * T))
+        pt, t2d = _transposed(plan)
+        dst = pt.col.long()
+        step = t2d.long() - plan.row_ptr.long()[dst]
+        from .plan import CsrPlan
+        memo[T] = CsrPlan(pt.row_ptr, (dst * T + step).to(torch.int32).contiguous(), pt.perm, pt.n_dst, plan.n_dst * T,
+                          pt.num_edges)
+    return memo[T]
+
+
+def lstm_aggregate_forward(plan, T, P, p_pad, R, saved=None, bad_flag=None):
+    """One launch of tfgx_lstm_aggregate_f32: [plan.n_dst, U] mean of h_t over the T steps of every row."""
+    lib = L.require_gpu()
+    P, ldp = L.row_major_2d(P)
+    R = R.contiguous()
+    U = int(R.shape[0])
+    out = torch.empty((plan.n_dst, U), dtype=torch.float32, device=P.device)
+    L.check(lib.tfgx_lstm_aggregate_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), plan.n_dst, plan.n_src, T, L.ptr(P), ldp,
+                                        L.ptr(p_pad.contiguous()), L.ptr(R), U, L.ptr(out), U, L.ptr(saved),
+                                        0 if saved is None else int(saved.numel()), L.ptr(bad_flag), L.stream_ptr()),
+            "tfgx_lstm_aggregate_f32")
+    return out
+
+
+class _LstmAggregate(torch.autograd.Function):
+    """mean_t h_t of the unmasked LSTM over every row's padded neighbour sequence, inputs (P, p_pad, R) (tfgx_lstm.h)."""
+
+    @staticmethod
+    def forward(ctx, plan, T, P, p_pad, R):
+        lib = L.require_gpu()
+        U = int(R.shape[0])
+        saved = torch.empty(max(lib.tfgx_lstm_aggregate_saved_bytes(plan.n_dst, T, U), 1), dtype=torch.uint8, device=P.device)
+        out = lstm_aggregate_forward(plan, T, P.detach(), p_pad.detach(), R.detach(), saved=saved)
+        ctx.plan, ctx.T, ctx.n_src = plan, T, int(P.shape[0])
+        ctx.save_for_backward(R, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.require_gpu()
+        plan, T = ctx.plan, ctx.T
+        R, saved = ctx.saved_tensors
+        R = R.detach().contiguous()
+        U = int(R.shape[0])
+        g, ldd = L.row_major_2d(g)
+        dev = g.device
+        if plan.n_dst == 0 or T == 0:
+            return (None, None, torch.zeros((ctx.n_src, 4 * U), dtype=torch.float32, device=dev),
+                    torch.zeros(4 * U, dtype=torch.float32, device=dev), torch.zeros_like(R))
+        d_gates = torch.empty((plan.n_dst * T, 4 * U), dtype=torch.float32, device=dev)
+        h_prev = torch.empty((plan.n_dst * T, U), dtype=torch.float32, device=dev)
+        d_pad = torch.empty((lib.tfgx_lstm_aggregate_tiles(plan.n_dst), 4 * U), dtype=torch.float32, device=dev)
+        L.check(lib.tfgx_lstm_aggregate_backward_f32(L.ptr(plan.row_ptr), plan.n_dst, T, U, L.ptr(R), L.ptr(g), ldd, L.ptr(saved),
+                                                     int(saved.numel()), L.ptr(d_gates), L.ptr(h_prev), L.ptr(d_pad),
+                                                     L.stream_ptr()), "tfgx_lstm_aggregate_backward_f32")
+        gP = gpad = gR = None
+        if ctx.needs_input_grad[2]:
+            if plan.num_edges > 0:
+                gP = segment_reduce(_lstm_step_plan(plan, T), d_gates, L.SUM)
+            else:
+                gP = torch.zeros((ctx.n_src, 4 * U), dtype=torch.float32, device=dev)
+        if ctx.needs_input_grad[3]:
+            gpad = column_sums(d_pad)
+        if ctx.needs_input_grad[4]:
+            gR = gemm_tn(h_prev, d_gates)[0]
+        return None, None, gP, gpad, gR
+
+
+def lstm_aggregate(plan, T, P, p_pad, R):
+    """[plan.n_dst, U]: the LSTM aggregator's neighbour term before neighbor_kernel.  P [plan.n_src, 4U] = x @ kernel + bias,
+    p_pad [4U] = the projection of a zero row, R [U, 4U]; U a multiple of 16 up to 256.  Differentiable in P, p_pad and R."""
+    if needs_grad(P, p_pad, R):
+        return _LstmAggregate.apply(plan, T, P, p_pad, R)
+    return lstm_aggregate_forward(plan, T, P, p_pad, R)

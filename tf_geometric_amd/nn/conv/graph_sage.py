@@ -1,6 +1,6 @@
 # coding=utf-8
 """GraphSAGE aggregators on the HIP backend — functional mirror of tf_geometric/nn/conv/graph_sage.py
-(mean / sum / gcn / mean-pool / max-pool; the LSTM aggregator is an RNN, not a segment reduce: out of scope).
+(mean / sum / gcn / mean-pool / max-pool on the segment-reduce kernels; lstm on the fused gather -> recurrence kernel).
 
 Reference quirks that are reproduced on purpose:
   * mean_pool / max_pool / gcn variants REPLACE a provided edge_weight by ones (:139-140, :190-191, :253-254) and
@@ -364,3 +364,59 @@ def max_pool_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_mlp_ke
     """Reference: graph_sage.py:228-287. An isolated node keeps float32 lowest() through the next GEMM."""
     return _pool_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_mlp_kernel, neighbor_kernel,
                             neighbor_mlp_bias, bias, activation, concat, normalize, L.MAX, cache)
+
+
+def _pad_gate_blocks(w, U, Up):
+    """[..., 4U] -> [..., 4Up]: every gate block (i, f, c, o) zero-padded from U to Up columns."""
+    if Up == U:
+        return w
+    lead = tuple(w.shape[:-1])
+    return torch.nn.functional.pad(w.reshape(lead + (4, U)), (0, Up - U)).reshape(lead + (4 * Up,))
+
+
+def lstm_graph_sage(x, edge_index, lstm, self_kernel, neighbor_kernel, bias=None, activation=None, concat=True,
+                    normalize=False, training=False, cache=None):
+    """Reference: graph_sage.py:290-356.  Node i's sequence is x[col] of its edges in the caller's edge order (the plan's sort
+    is stable; the reference's argsort leaves ties unspecified) followed by T - deg(i) zero rows, T the largest degree; the
+    LSTM is not masked and reduced_h is the mean of h_t over all T steps.  `lstm`: anything with .kernel [F, 4U],
+    .recurrent_kernel [U, 4U] and .bias [4U] (Keras layout, gates i, f, c, o) — layers.LSTM builds itself on first use.
+    `training` changes nothing (no dropout), as in the reference's layer.
+    The input projection P = x @ kernel + bias is one GEMM; tfgx_lstm_aggregate_f32 owns the recurrence.
+    Units that are no multiple of 16 are zero-padded to the next one (exact: a padded unit stays at h = c = 0 and its zero
+    rows of the recurrent kernel feed nothing).  No edges (T = 0): the neighbour term is zeros (the reference takes the mean
+    of an empty axis).  A plan with fewer destinations than x has rows takes x[:n_dst] as the self term."""
+    _refuse_half(x, "lstm_graph_sage")
+    x = L.as_f32(x)
+    n = int(x.shape[0])
+    if hasattr(lstm, "_maybe_build"):
+        lstm._maybe_build([x])
+    kernel, rk, lb = L.as_f32(lstm.kernel), L.as_f32(lstm.recurrent_kernel), L.as_f32(lstm.bias)
+    U = int(rk.shape[0])
+    if tuple(kernel.shape) != (int(x.shape[1]), 4 * U) or tuple(rk.shape) != (U, 4 * U) or tuple(lb.shape) != (4 * U,):
+        raise ValueError("lstm_graph_sage: lstm weights must be kernel [F, 4U], recurrent_kernel [U, 4U], bias [4U]; got {}, {}, {}"
+                         .format(tuple(kernel.shape), tuple(rk.shape), tuple(lb.shape)))
+    Up = (U + 15) // 16 * 16
+    if Up > L.LSTM_MAX_UNITS:
+        raise NotImplementedError("lstm_graph_sage: {} LSTM units (padded to {}) exceed the kernel's limit of {}".format(
+            U, Up, L.LSTM_MAX_UNITS))
+    plan = CsrPlan.from_cache(edge_index, n, n, cache)
+    if plan.n_src != n or plan.n_dst > n:
+        raise ValueError("lstm_graph_sage: the plan is [{} x {}] but x has {} rows".format(plan.n_dst, plan.n_src, n))
+    T = AG.lstm_max_degree(plan)
+    ws, wn = L.as_f32(self_kernel), L.as_f32(neighbor_kernel)
+    x_self = x if plan.n_dst == n else x[:plan.n_dst]
+    if T == 0:
+        reduced = torch.zeros((plan.n_dst, U), dtype=torch.float32, device=x.device)
+    else:
+        kp, bp = _pad_gate_blocks(kernel, U, Up), _pad_gate_blocks(lb, U, Up)
+        rp = _pad_gate_blocks(rk, U, Up)
+        if Up != U:
+            rp = torch.nn.functional.pad(rp, (0, 0, 0, Up - U))
+        if AG.needs_grad(x, kp, bp, rp):
+            P = AG.linear(x, kp, bp, gathered=True)
+        else:
+            P = gemm_bias_act(x, kp, bias=bp.contiguous(), out=gather_friendly_empty(n, 4 * Up, x.device))
+        reduced = AG.lstm_aggregate(plan, T, P, bp, rp)
+        if Up != U:
+            reduced = reduced[:, :U]
+    return _combine(ws, x_self, wn, reduced, bias, activation, concat, normalize)
