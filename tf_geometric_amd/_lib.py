@@ -312,6 +312,23 @@ LSTM_SIGNATURES = {
     "tfgx_lstm_aggregate_backward_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _P, _P]),
 }
 
+# include/tfgx_set2set.h (Set2Set: the per-graph attention readout and the stateful sequence LSTM, each with its backward):
+# its own header, version and table — checked against that header by tests/test_set2set_abi.py.
+SET2SET_ABI_VERSION = 1
+SET2SET_CHUNK_ROWS = 512
+SET2SET_MAX_FEATURES = 1024
+SET2SET_SIGNATURES = {
+    "tfgx_set2set_version": (ctypes.c_int, []),
+    "tfgx_set2set_attend_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "tfgx_set2set_attend_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _SZ, _P, _P]),
+    "tfgx_set2set_attend_backward_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _I64,
+                                                        _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "tfgx_lstm_sequence_kernel_resident": (ctypes.c_int, [_I64]),
+    "tfgx_lstm_sequence_saved_bytes": (_SZ, [_I64, _I64, _I64]),
+    "tfgx_lstm_sequence_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "tfgx_lstm_sequence_backward_f32": (ctypes.c_int, [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -355,6 +372,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in SET2SET_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_set2set_version() != SET2SET_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_set2set ABI {} but this package binds {} "
+                        "(include/tfgx_set2set.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_set2set_version(), SET2SET_ABI_VERSION))
     if lib.tfgx_lstm_version() != LSTM_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_lstm ABI {} but this package binds {} "
                         "(include/tfgx_lstm.h): rebuild with __graft_entry__.build()".format(

@@ -1399,3 +1399,123 @@ def lstm_aggregate(plan, T, P, p_pad, R):
     if needs_grad(P, p_pad, R):
         return _LstmAggregate.apply(plan, T, P, p_pad, R)
     return lstm_aggregate_forward(plan, T, P, p_pad, R)
+
+
+# ---- Set2Set (include/tfgx_set2set.h): the stateful sequence LSTM and the per-graph attention readout
+def lstm_sequence_forward(P, B, T, R, h0=None, c0=None, saved=None):
+    """One launch of tfgx_lstm_sequence_f32 over P [B * T, 4U]: (h_seq [B * T, U], h_last [B, U], c_last [B, U])."""
+    lib = L.require_gpu()
+    P, ldp = L.row_major_2d(P)
+    R = R.contiguous()
+    U = int(R.shape[0])
+    dev = P.device
+    h_seq = torch.empty((B * T, U), dtype=torch.float32, device=dev)
+    h_last = torch.empty((B, U), dtype=torch.float32, device=dev)
+    c_last = torch.empty((B, U), dtype=torch.float32, device=dev)
+    L.check(lib.tfgx_lstm_sequence_f32(L.ptr(P), ldp, B, T, L.ptr(R), U, L.ptr(h0), L.ptr(c0), L.ptr(h_seq), L.ptr(h_last),
+                                       L.ptr(c_last), L.ptr(saved), 0 if saved is None else int(saved.numel()), L.stream_ptr()),
+            "tfgx_lstm_sequence_f32")
+    return h_seq, h_last, c_last
+
+
+class _LstmSequence(torch.autograd.Function):
+    """(h_seq, h_last, c_last) of an LSTM over B sequences of T steps with the input projection P hoisted and an initial
+    state (h0, c0) (tfgx_set2set.h).  dP is the kernel's d_gates itself, dR = h_prev^T @ d_gates on the gemm_tn kernel."""
+
+    @staticmethod
+    def forward(ctx, P, B, T, R, h0, c0):
+        lib = L.require_gpu()
+        U = int(R.shape[0])
+        h0d, c0d = h0.detach().contiguous(), c0.detach().contiguous()
+        saved = torch.empty(max(lib.tfgx_lstm_sequence_saved_bytes(B, T, U), 1), dtype=torch.uint8, device=P.device)
+        out = lstm_sequence_forward(P.detach(), B, T, R.detach(), h0d, c0d, saved=saved)
+        ctx.B, ctx.T = B, T
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(R, h0d, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_seq, g_h, g_c):
+        lib = L.require_gpu()
+        B, T = ctx.B, ctx.T
+        R, h0, saved = ctx.saved_tensors
+        R = R.detach().contiguous()
+        U = int(R.shape[0])
+        dev = R.device
+        g_seq, g_h, g_c = (None if g is None else g.to(torch.float32).contiguous() for g in (g_seq, g_h, g_c))
+        d_gates = torch.empty((B * T, 4 * U), dtype=torch.float32, device=dev)
+        h_prev = torch.empty((B * T, U), dtype=torch.float32, device=dev)
+        d_h0 = torch.empty((B, U), dtype=torch.float32, device=dev)
+        d_c0 = torch.empty((B, U), dtype=torch.float32, device=dev)
+        L.check(lib.tfgx_lstm_sequence_backward_f32(B, T, U, L.ptr(R), L.ptr(h0), L.ptr(g_seq), L.ptr(g_h), L.ptr(g_c),
+                                                    L.ptr(saved), int(saved.numel()), L.ptr(d_gates), L.ptr(h_prev),
+                                                    L.ptr(d_h0), L.ptr(d_c0), L.stream_ptr()), "tfgx_lstm_sequence_backward_f32")
+        need = ctx.needs_input_grad
+        gR = gemm_tn(h_prev, d_gates)[0] if need[3] else None
+        return (d_gates if need[0] else None), None, None, gR, (d_h0 if need[4] else None), (d_c0 if need[5] else None)
+
+
+def lstm_sequence(P, B, T, R, h0, c0):
+    """(h_seq [B * T, U], h_last, c_last [B, U]); P [B * T, 4U] (row b * T + t), R [U, 4U], h0 / c0 [B, U]; U a multiple of 16
+    up to 256, B * T > 0.  Differentiable in P, R, h0 and c0."""
+    if needs_grad(P, R, h0, c0):
+        return _LstmSequence.apply(P, B, T, R, h0, c0)
+    return lstm_sequence_forward(P, B, T, R, h0.contiguous(), c0.contiguous())
+
+
+def set2set_attend_forward(plan, x, q, stats=None, bad_flag=None):
+    """One tfgx_set2set_attend_f32 call on a graph plan (rows = graphs, col = node ids): r [G, F]."""
+    lib = L.require_gpu()
+    x, ldx = L.row_major_2d(x)
+    q, ldq = L.row_major_2d(q)
+    G, N, F = plan.n_dst, int(x.shape[0]), int(x.shape[1])
+    r = torch.empty((G, F), dtype=torch.float32, device=x.device)
+    ws_bytes = lib.tfgx_set2set_attend_workspace_bytes(N, G, F)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    L.check(lib.tfgx_set2set_attend_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), G, N, L.ptr(x), ldx, F, L.ptr(q), ldq, L.ptr(r),
+                                        max(F, 1), L.ptr(stats), L.ptr(ws), ws_bytes, L.ptr(bad_flag), L.stream_ptr()),
+            "tfgx_set2set_attend_f32")
+    return r
+
+
+class _Set2SetAttend(torch.autograd.Function):
+    """r_g = sum_n softmax_g(<x_n, q_g>) x_n with the reference's epsilon (segment.py:26-33): one pass over x forward, one
+    pass backward (tfgx_set2set.h).  The statistics (m, D) are kept only here, where gradients are recorded."""
+
+    @staticmethod
+    def forward(ctx, plan, x, q):
+        xd, qd = x.detach(), q.detach()
+        stats = torch.empty((plan.n_dst, 2), dtype=torch.float32, device=xd.device)
+        r = set2set_attend_forward(plan, xd, qd, stats=stats)
+        ctx.plan = plan
+        ctx.save_for_backward(xd, qd, r, stats)
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.require_gpu()
+        plan = ctx.plan
+        x, q, r, stats = ctx.saved_tensors
+        x, ldx = L.row_major_2d(x)
+        q, ldq = L.row_major_2d(q)
+        g, ldg = L.row_major_2d(g.to(torch.float32))
+        G, N, F = plan.n_dst, int(x.shape[0]), int(x.shape[1])
+        d_x = None
+        if ctx.needs_input_grad[1]:
+            # every row has exactly one writer when the plan names every node; rows it skips must read as zero
+            d_x = (torch.empty if plan.num_edges == N else torch.zeros)((N, F), dtype=torch.float32, device=x.device)
+        d_q = torch.empty((G, F), dtype=torch.float32, device=x.device)
+        ws_bytes = lib.tfgx_set2set_attend_workspace_bytes(N, G, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+        L.check(lib.tfgx_set2set_attend_backward_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), G, N, L.ptr(x), ldx, F, L.ptr(q), ldq,
+                                                     L.ptr(r), max(F, 1), L.ptr(stats), L.ptr(g), ldg, L.ptr(d_x), max(F, 1),
+                                                     L.ptr(d_q), max(F, 1), L.ptr(ws), ws_bytes, L.stream_ptr()),
+                "tfgx_set2set_attend_backward_f32")
+        return None, d_x, (d_q if ctx.needs_input_grad[2] else None)
+
+
+def set2set_attend(plan, x, q):
+    """[G, F] attention readout of x [N, F] under the queries q [G, F]; plan = the graph plan of node_graph_index."""
+    if needs_grad(x, q):
+        return _Set2SetAttend.apply(plan, x, q)
+    return set2set_attend_forward(plan, x, q)

@@ -1,3 +1,4 @@
 # coding=utf-8
 from .readout import CommonPool, MeanPool, SumPool, MaxPool, MinPool
 from .sag_pool import SAGPool, SortPool
+from .set2set import Set2Set

@@ -3,3 +3,4 @@ from .common_pool import mean_pool, sum_pool, max_pool, min_pool
 from .topk_pool import topk_pool
 from .sag_pool import sag_pool
 from .sort_pool import sort_pool
+from .set2set import set2set
