@@ -46,7 +46,7 @@ def main(nodes=20000, steps=40, rate=0.5):
     # the full graph's plan and transposed plan: built (sorted) once; DropEdge derives every step's plans from them
     plan = CsrPlan.build(edge_index, nodes, nodes)
     plan.transposed()
-    edge_index._tfgx_plan = plan
+    tfg.plan.attach_plan(edge_index, plan)
 
     drop = tfg.layers.DropEdge(rate)
     gcn0, gcn1 = tfg.layers.GCN(32, activation=tfg.relu), tfg.layers.GCN(classes)

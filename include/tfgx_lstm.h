@@ -64,7 +64,7 @@ int tfgx_lstm_aggregate_f32(const int32_t* row_ptr, const int32_t* col, int64_t 
  *   d_gates [n_dst * T, 4U]: dz of (row i, step t) at row i * T + t    (the gradient of the gathered P row / of p_pad)
  *   h_prev  [n_dst * T, U]:  h_{t-1} of (row i, step t) at row i * T + t     (so dR = h_prev^T @ d_gates)
  *   d_pad_partial [tfgx_lstm_aggregate_tiles(n_dst), 4U]: each tile's sum of dz over its pad positions (t >= deg(i)), added in
- *   a fixed order; d p_pad is the column sum of this matrix.
+ *   a fixed order with a compensated (Kahan) running sum per lane; d p_pad is the column sum of this matrix.
  * A forward that raised bad_flag has no defined backward.  n_dst == 0, T == 0 or U == 0: nothing is done. */
 int tfgx_lstm_aggregate_backward_f32(const int32_t* row_ptr, int64_t n_dst, int64_t T, int64_t U, const float* R,
                                      const float* d_mean, int64_t ldd, const void* saved, size_t saved_bytes,

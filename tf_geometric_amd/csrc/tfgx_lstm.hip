@@ -238,12 +238,14 @@ __global__ void __launch_bounds__(kBlock) lstm_backward_kernel(const int32_t* __
 
     const float tf = float(T);
     float dm[kMaxBlocksPerWave][kRowTiles][4], dh_rec[kMaxBlocksPerWave][kRowTiles][4], dc_next[kMaxBlocksPerWave][kRowTiles][4];
-    float padacc[kMaxBlocksPerWave][4];
+    // a lane's pad sum runs over 8 rows x up to T steps, one term after the other: compensated (Kahan), or its rounding error
+    // grows with T and passes that of the rest of the backward at T of a few dozen (hub rows of a pooled graph)
+    float padacc[kMaxBlocksPerWave][4], padcmp[kMaxBlocksPerWave][4];
 #pragma unroll
     for (int q = 0; q < kMaxBlocksPerWave; ++q) {
         const int jb = wave + q * (kBlock / kWave);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) padacc[q][g] = 0.0f;
+        for (int g = 0; g < 4; ++g) padacc[q][g] = padcmp[q][g] = 0.0f;
 #pragma unroll
         for (int rt = 0; rt < kRowTiles; ++rt)
 #pragma unroll
@@ -292,7 +294,12 @@ __global__ void __launch_bounds__(kBlock) lstm_backward_kernel(const int32_t* __
                             h_prev[it * int64_t(U) + u] = hp;
                             if (t >= deg[rt][r]) {
 #pragma unroll
-                                for (int g = 0; g < 4; ++g) padacc[q][g] += dz[g];
+                                for (int g = 0; g < 4; ++g) {
+                                    const float y = dz[g] - padcmp[q][g];
+                                    const float sum = padacc[q][g] + y;
+                                    padcmp[q][g] = (sum - padacc[q][g]) - y;
+                                    padacc[q][g] = sum;
+                                }
                             }
                         }
 #pragma unroll

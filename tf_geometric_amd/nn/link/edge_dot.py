@@ -8,7 +8,7 @@ import torch
 
 from ... import _lib as L
 from ... import autograd as AG
-from ...plan import CsrPlan
+from ...plan import CsrPlan, attach_plan, attached_plan
 
 
 def _range_checked(edge_index, n_a, n_b):
@@ -45,8 +45,8 @@ def edge_dot(z, edge_index, z_other=None, cache=None):
         if plan.num_edges != E or plan.n_dst != n_a or plan.n_src != n_b:
             raise ValueError("edge_dot: the plan found in cache / on edge_index describes a [{}, {}] operator with {} edges, "
                              "this call needs [{}, {}] with {}".format(plan.n_dst, plan.n_src, plan.num_edges, n_a, n_b, E))
-        if cache is None and isinstance(edge_index, torch.Tensor) and getattr(edge_index, "_tfgx_plan", None) is None:
-            edge_index._tfgx_plan = plan
+        if cache is None and isinstance(edge_index, torch.Tensor) and attached_plan(edge_index) is None:
+            attach_plan(edge_index, plan)
         return AG.edge_dot(plan, a, None if z_other is None else b, row, col)
     if _range_checked(edge_index, n_a, n_b):
         return AG.edge_dot_forward(a.detach(), b.detach(), row, col)

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ...plan import attach_plan, attached_plan
 from ...utils.subgraph import pool_graph, parent_plan_of, refuse_capture
 from .topk_pool import topk_pool
 
@@ -14,11 +15,10 @@ from .topk_pool import topk_pool
 def _with_plan(edge_index, plan):
     """edge_index as handed to the score GNN: a tensor carrying the parent plan (an alias, so the caller's tensor object is
     left alone), so the GNN does not sort the edge list again.  numpy stays as given."""
-    if not isinstance(edge_index, torch.Tensor) or getattr(edge_index, "_tfgx_plan", None) is not None:
+    if not isinstance(edge_index, torch.Tensor) or attached_plan(edge_index) is not None:
         return edge_index
-    alias = edge_index.view(edge_index.shape)
-    alias._tfgx_plan = plan
-    return alias
+    alias = edge_index.view(edge_index.shape)      # shares the caller's storage AND version counter
+    return attach_plan(alias, plan)
 
 
 def sag_pool(x, edge_index, edge_weight, node_graph_index, score_gnn, k=None, ratio=None, score_activation=None,

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ...plan import attached_plan
 from ...utils.subgraph import pool_graph, refuse_capture
 from .topk_pool import topk_pool
 
@@ -21,6 +22,6 @@ def sort_pool(x, edge_index, edge_weight, node_graph_index, k=None, ratio=None, 
     xt = L.as_f32(x)
     score = xt.detach()[:, sort_index]                                                              # :26
     topk_node_index = topk_pool(L.as_i32(node_graph_index), score, k=k, ratio=ratio)                # :27
-    plan = getattr(edge_index, "_tfgx_plan", None) if isinstance(edge_index, torch.Tensor) else None
+    plan = attached_plan(edge_index)
     return list(pool_graph(xt, edge_index, edge_weight, node_graph_index, topk_node_index, int(np.shape(x)[0]),
                            plan=plan, x_numpy=not isinstance(x, torch.Tensor)))                     # :29-35

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
-from ...plan import CsrPlan, CACHE_KEY_PLAN
+from ...plan import CsrPlan, CACHE_KEY_PLAN, attach_plan, attached_plan
 from ...utils.subgraph import refuse_capture
 
 # Dispatch between deriving the dropped list's plans from the parent's (True) and sorting the dropped list again
@@ -37,7 +37,7 @@ def _seed_from_torch():
 
 
 def _parent_plan(edge_index, num_edges, cache):
-    plan = getattr(edge_index, "_tfgx_plan", None)
+    plan = attached_plan(edge_index, num_edges)
     if plan is None and cache is not None:
         plan = cache.get(CACHE_KEY_PLAN, None)
     if plan is not None and plan.num_edges != num_edges:
@@ -165,5 +165,5 @@ def drop_edge(inputs, rate=0.5, force_undirected=False, training=None, seed=None
     if as_numpy:
         out = out.cpu().numpy()
     elif plan is not None:
-        out._tfgx_plan = plan       # CsrPlan.from_cache / SparseMatrix.plan pick it up: no sort in the next layer
+        attach_plan(out, plan)      # CsrPlan.from_cache / SparseMatrix.plan pick it up: no sort in the next layer
     return [out] + dropped_attrs

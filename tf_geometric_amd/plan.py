@@ -14,6 +14,38 @@ from . import _lib as L
 CACHE_KEY_PLAN = "tfgx_csr_plan"
 
 
+def attach_plan(edge_index, plan):
+    """Hand `plan` on with the edge list it describes: edge_index._tfgx_plan = plan, together with the tensor's version
+    counter at this moment.  Producers call it AFTER their kernels have written the list through raw pointers, so the recorded
+    version is the one the consumers see."""
+    edge_index._tfgx_plan = plan
+    edge_index._tfgx_plan_version = edge_index._version
+    return edge_index
+
+
+def attached_plan(edge_index, num_edges=None):
+    """The plan a producer attached to `edge_index` (attach_plan), or None: no tensor, no attachment, a plan of another edge
+    count (`num_edges`, default edge_index.shape[1]), or a tensor written to in place since the plan was attached (torch's
+    version counter — `ei += offset`, `ei[0, i] = j`): the plan then describes the OLD graph and is never used.  The one place
+    that reads the attribute.  A plan a caller stored as `edge_index._tfgx_plan = plan` without attach_plan is taken as
+    attached at its first sighting here."""
+    if not isinstance(edge_index, torch.Tensor):
+        return None
+    plan = getattr(edge_index, "_tfgx_plan", None)
+    if plan is None:
+        return None
+    if num_edges is None:
+        num_edges = int(edge_index.shape[1]) if edge_index.dim() == 2 else 0
+    if plan.num_edges != int(num_edges):
+        return None
+    version = getattr(edge_index, "_tfgx_plan_version", None)
+    if version is None:
+        edge_index._tfgx_plan_version = edge_index._version
+    elif version != edge_index._version:
+        return None
+    return plan
+
+
 class CsrPlan(object):
     """row_ptr[n_dst+1], col[E] (source per CSR position), perm[E] (CSR position -> original edge id)."""
 
@@ -69,6 +101,15 @@ class CsrPlan(object):
             return self
         if n_dst < self.n_dst or n_src < self.n_src:
             return None
+        plan = self._widened(n_dst, n_src)
+        if self._transposed is not None:
+            # a transposed plan that was handed on with this one (drop_edge derives both) is widened with it, as the
+            # [n_src, n_dst] operator: the backward pass of the consumer does not sort the flipped list again
+            plan._transposed = self._transposed._widened(n_src, n_dst)
+            plan._transposed._transposed = plan
+        return plan
+
+    def _widened(self, n_dst, n_src):
         tail = self.row_ptr[-1:].expand(n_dst - self.n_dst)
         plan = CsrPlan(torch.cat([self.row_ptr, tail]).contiguous(), self.col, self.perm, n_dst, n_src, self.num_edges)
         plan._edge_index = self._edge_index
@@ -81,7 +122,7 @@ class CsrPlan(object):
             plan = cache.get(key, None)
             if plan is not None:
                 return plan
-        attached = getattr(edge_index, "_tfgx_plan", None)      # a producer that already knows the CSR (the sampler)
+        attached = attached_plan(edge_index)      # a producer that already knows the CSR (the sampler, pooling, drop_edge)
         plan = attached.padded_to(n_dst, n_dst if n_src is None else n_src) if attached is not None else None
         if plan is None:
             plan = CsrPlan.build(edge_index, n_dst, n_src)

@@ -7,13 +7,13 @@ are the ones the reference's call sites rely on (nn/conv/gcn.py:72-98,262,280; n
 import torch
 
 from . import _lib as L
-from .plan import CsrPlan, segment_reduce
+from .plan import CsrPlan, segment_reduce, attached_plan
 
 
 class SparseMatrix(object):
     def __init__(self, index, value=None, shape=None):
-        self._attached_plan = getattr(index, "_tfgx_plan", None)    # a producer that already knows the CSR (the sampler,
-        self.index = L.as_i32(index)                                # a pooling layer): CsrPlan.from_cache's rule
+        self._index_given = index         # a producer that already knows the CSR (the sampler, a pooling layer) attached its
+        self.index = L.as_i32(index)      # plan to this tensor: CsrPlan.from_cache's rule, asked when the plan is needed
         if self.index.numel() == 0:
             self.index = self.index.reshape(2, 0)
         E = int(self.index.shape[1])
@@ -34,7 +34,7 @@ class SparseMatrix(object):
     @property
     def plan(self):
         if self._plan is None:
-            attached = self._attached_plan
+            attached = attached_plan(self._index_given)
             plan = attached.padded_to(self._shape[0], self._shape[1]) if attached is not None else None
             self._plan = plan if plan is not None else CsrPlan.build(self.index, self._shape[0], self._shape[1])
         return self._plan

@@ -138,7 +138,8 @@ def pool_graph(x, edge_index, edge_weight, node_graph_index, node_index, num_nod
     if ei_np:
         pei = pei.cpu().numpy()
     elif sub.plan is not None:
-        pei._tfgx_plan = sub.plan       # CsrPlan.from_cache / SparseMatrix.plan pick it up: no sort in the next layer
+        from ..plan import attach_plan
+        attach_plan(pei, sub.plan)      # CsrPlan.from_cache / SparseMatrix.plan pick it up: no sort in the next layer
     return px, pei, pw, pgi
 
 
@@ -170,6 +171,7 @@ def sample_new_graph_by_node_index(edge_index, sampled_node_index, x=None, edge_
         n = int(np.shape(node_graph_index)[0])
     else:
         n = max(int(ei.max().item()) if ei.numel() else -1, int(idx.max().item()) if idx.numel() else -1) + 1
-    plan = getattr(edge_index, "_tfgx_plan", None)      # a pooled / sampled edge list hands its plan on
+    from ..plan import attached_plan
+    plan = attached_plan(edge_index)      # a pooled / sampled edge list hands its plan on
     return pool_graph(x, edge_index, edge_weight, node_graph_index, idx, n, plan=plan,
                       x_numpy=x is not None and not isinstance(x, torch.Tensor))
