@@ -329,6 +329,23 @@ SET2SET_SIGNATURES = {
     "tfgx_lstm_sequence_backward_f32": (ctypes.c_int, [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P]),
 }
 
+# include/tfgx_asap.h (ASAP pooling: the fused 1-hop attention with its backward, and the sparse S^T A S of cluster_pool): its
+# own header, version and table — checked against that header by tests/test_asap_abi.py.
+ASAP_ABI_VERSION = 1
+ASAP_MAX_FEATURES = 256
+_PI64 = ctypes.POINTER(ctypes.c_int64)
+ASAP_SIGNATURES = {
+    "tfgx_asap_version": (ctypes.c_int, []),
+    "tfgx_asap_attend_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _F32, _U64, _P, _I64, _P, _P, _P, _P,
+                                            _P, _P]),
+    "tfgx_asap_attend_backward_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tfgx_spasp_count_workspace_bytes": (_SZ, [_I64, _I64]),
+    "tfgx_spasp_workspace_bytes": (_SZ, [_I64, _I64]),
+    "tfgx_spasp_count": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _PI64, _P, _SZ, _P]),
+    "tfgx_spasp_emit": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _SZ, _P]),
+    "tfgx_spasp_reduce": (ctypes.c_int, [_I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+
 _lib = None
 
 
@@ -376,6 +393,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in ASAP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_asap_version() != ASAP_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_asap ABI {} but this package binds {} "
+                        "(include/tfgx_asap.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_asap_version(), ASAP_ABI_VERSION))
     if lib.tfgx_set2set_version() != SET2SET_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_set2set ABI {} but this package binds {} "
                         "(include/tfgx_set2set.h): rebuild with __graft_entry__.build()".format(

@@ -1519,3 +1519,128 @@ def set2set_attend(plan, x, q):
     if needs_grad(x, q):
         return _Set2SetAttend.apply(plan, x, q)
     return set2set_attend_forward(plan, x, q)
+
+
+def dropout_keep_scale(seed, positions, rate):
+    """tfgx_dropout_keep(seed, position, rate) / (1 - rate) for an int64 tensor of positions, as torch integer arithmetic on
+    the device (csrc/tfgx_common.h drop_hash: murmur3's finaliser over position ^ seed_lo, seed_hi mixed in between the two
+    multiplies; keep <=> top 24 bits >= rate * 2^24).  The statement of the in-kernel mask for the composed routes."""
+    import numpy as np
+    m = 0xFFFFFFFF
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    v = (positions.to(torch.int64) & m) ^ (seed & m)
+    v = v ^ (v >> 16)
+    v = (v * 0x85ebca6b) & m
+    v = v ^ (seed >> 32)
+    v = v ^ (v >> 13)
+    v = (v * 0xc2b2ae35) & m
+    v = v ^ (v >> 16)
+    thr = int(np.float32(rate) * np.float32(16777216.0))
+    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(rate)))
+    return ((v >> 8) >= thr).to(torch.float32) * scale
+
+
+def plan_rows(plan):
+    """int64 [E]: the destination row of every CSR position (no host read: the output size is the plan's edge count)."""
+    if getattr(plan, "_rows64", None) is None:
+        ar = torch.arange(plan.n_dst, dtype=torch.int64, device=plan.col.device)
+        plan._rows64 = torch.repeat_interleave(ar, plan.in_degree().to(torch.int64), output_size=plan.num_edges)
+    return plan._rows64
+
+
+def asap_attend_forward(plan, x, sq, sh, bias, drop_rate=0.0, seed=0, bad_flag=None):
+    """One tfgx_asap_attend_f32 call on a square plan: (c [N, F], p [E], p_self [N], p_drop, p_self_drop) — the last two are
+    None without dropout (they would equal p and p_self)."""
+    lib = L.require_gpu()
+    x, ldx = L.row_major_2d(x)
+    N, E, F = plan.n_dst, plan.num_edges, int(x.shape[1])
+    dev = x.device
+    c = torch.empty((N, F), dtype=torch.float32, device=dev)
+    p = torch.empty(E, dtype=torch.float32, device=dev)
+    p_self = torch.empty(N, dtype=torch.float32, device=dev)
+    pd = pds = None
+    if drop_rate > 0.0:
+        pd, pds = torch.empty_like(p), torch.empty_like(p_self)
+    L.check(lib.tfgx_asap_attend_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(x), ldx, F, L.ptr(sq), L.ptr(sh),
+                                     L.ptr(bias), float(drop_rate), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(c), max(F, 1),
+                                     L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds), L.ptr(bad_flag), L.stream_ptr()),
+            "tfgx_asap_attend_f32")
+    return c, p, p_self, pd, pds
+
+
+class _AsapAttend(torch.autograd.Function):
+    """ASAP's 1-hop attention (include/tfgx_asap.h): c_i = sum_e k_e p_e x[col_e] over row i and its implicit self edge, with
+    p = softmax_i(leaky_relu(sq_i + sh[col_e] + bias)).  Returns (c, k p [E], k p of the self edges [N]); only c carries a
+    gradient (the weights feed the detached assignment).  Backward: d/dx on the transposed plan with k p as weights,
+    dp_e = <g_i, x[col_e]> on the SDDMM kernel (both existing), then ONE launch for the softmax / leaky-relu backward."""
+
+    @staticmethod
+    def forward(ctx, plan, x, sq, sh, bias, drop_rate, seed):
+        xd = x.detach()
+        sqd, shd, bd = sq.detach().contiguous(), sh.detach().contiguous(), bias.detach().contiguous()
+        c, p, p_self, pd, pds = asap_attend_forward(plan, xd, sqd, shd, bd, drop_rate, seed)
+        ctx.plan = plan
+        ctx.save_for_backward(xd, sqd, shd, bd, p, p_self, pd, pds)
+        pw, pws = (p, p_self) if pd is None else (pd, pds)
+        ctx.mark_non_differentiable(pw, pws)
+        return c, pw, pws
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gps):
+        lib = L.require_gpu()
+        plan = ctx.plan
+        x, sq, sh, bias, p, p_self, pd, pds = ctx.saved_tensors
+        pw, pws = (p, p_self) if pd is None else (pd, pds)
+        need_x = ctx.needs_input_grad[1]
+        need_s = any(ctx.needs_input_grad[2:5])
+        g = g.to(torch.float32).contiguous()
+        gx, dp, dps = _aggregate_backward(plan, False, x, pw, pws, g, need_x, need_s, need_s)
+        if not need_s:
+            return None, gx, None, None, None, None, None
+        N, E = plan.n_dst, plan.num_edges
+        ds = torch.empty(E, dtype=torch.float32, device=g.device)
+        ds_self = torch.empty(N, dtype=torch.float32, device=g.device)
+        dsq = torch.empty(N, dtype=torch.float32, device=g.device)
+        L.check(lib.tfgx_asap_attend_backward_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(sq), L.ptr(sh), L.ptr(bias),
+                                                  L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds), L.ptr(dp.contiguous()),
+                                                  L.ptr(dps.contiguous()), L.ptr(ds), L.ptr(ds_self), L.ptr(dsq),
+                                                  L.stream_ptr()), "tfgx_asap_attend_backward_f32")
+        # d sh_j = sum of ds over the edges that point AT j, plus j's self edge: a segment sum on the transposed plan
+        pt, t2d = _transposed(plan)
+        ones = torch.ones((N, 1), dtype=torch.float32, device=g.device)
+        dsh = segment_reduce(pt, ones, L.SUM, w_csr=_permute(ds, t2d) if E else ds, self_coef=ds_self)[:, 0]
+        return None, gx, dsq, dsh.contiguous(), dsq.sum().reshape(1), None, None
+
+
+def asap_attend_composed(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
+    """The same attention from operators that were here before the fused launch: two scalar gathers, leaky_relu, the
+    segment softmax kernel over the row ids (explicit self edges appended), dropout by dropout_keep_scale and the weighted
+    aggregation.  Used past TFGX_ASAP_MAX_FEATURES and as the comparator of tests / tools/bench_asap.py; makes [E]-sized
+    intermediates only ([E, 2A] is avoided by the split of the score kernel, as in the fused route)."""
+    from .nn.kernel.segment import segment_softmax as _segment_softmax
+    N, E = plan.n_dst, plan.num_edges
+    rows = plan_rows(plan)
+    ar = torch.arange(N, dtype=torch.int64, device=x.device)
+    z = torch.cat([sq[rows] + sh[plan.col.long()], sq + sh]) + bias
+    s = torch.nn.functional.leaky_relu(z, 0.2)
+    prob = _segment_softmax(s, torch.cat([rows, ar]).to(torch.int32), N)
+    if drop_rate > 0.0:
+        prob = prob * dropout_keep_scale(seed, torch.arange(E + N, dtype=torch.int64, device=x.device), drop_rate)
+    pw, pws = prob[:E], prob[E:]
+    c = aggregate(plan, x, L.SUM, w_csr=pw.contiguous(), self_coef=pws.contiguous())
+    return c, pw.detach(), pws.detach()
+
+
+ASAP_FUSED = True      # developer A/B switch: False sends every width down the composed route
+
+
+def asap_attend(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
+    """(c [N, F], k p [E] in the plan's CSR order, k p of the self edges [N]) — the fused launch up to
+    TFGX_ASAP_MAX_FEATURES columns, the composed route past it.  sq, sh: [N]; bias: [1]."""
+    if ASAP_FUSED and int(x.shape[1]) <= L.ASAP_MAX_FEATURES:
+        if needs_grad(x, sq, sh, bias):
+            return _AsapAttend.apply(plan, x, sq, sh, bias, float(drop_rate), int(seed))
+        c, p, p_self, pd, pds = asap_attend_forward(plan, x.detach(), sq.detach().contiguous(), sh.detach().contiguous(),
+                                                    bias.detach().contiguous(), drop_rate, seed)
+        return (c, p, p_self) if pd is None else (c, pd, pds)
+    return asap_attend_composed(plan, x, sq, sh, bias, drop_rate, seed)

@@ -2,3 +2,4 @@
 from .readout import CommonPool, MeanPool, SumPool, MaxPool, MinPool
 from .sag_pool import SAGPool, SortPool
 from .set2set import Set2Set
+from .asap import ASAP

@@ -9,6 +9,6 @@ from .conv.gat import gat
 from .conv.graph_sage import (mean_graph_sage, sum_graph_sage, gcn_graph_sage, mean_pool_graph_sage,
                               max_pool_graph_sage, lstm_graph_sage)
 from .conv.propagation import gin, sgc, tagcn, appnp, ssgc, chebynet, le_conv, chebynet_norm_edge
-from .pool import mean_pool, sum_pool, max_pool, min_pool, topk_pool, sag_pool, sort_pool, set2set
+from .pool import mean_pool, sum_pool, max_pool, min_pool, topk_pool, sag_pool, sort_pool, set2set, cluster_pool, asap
 from .sampling import drop_edge
 from .link import edge_dot

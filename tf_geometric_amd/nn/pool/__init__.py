@@ -4,3 +4,5 @@ from .topk_pool import topk_pool
 from .sag_pool import sag_pool
 from .sort_pool import sort_pool
 from .set2set import set2set
+from .cluster_pool import cluster_pool
+from .asap import asap

@@ -7,12 +7,16 @@ import torch
 from ... import _lib as L
 
 
-def topk_pool(source_index, score, k=None, ratio=None):
+def topk_pool(source_index, score, k=None, ratio=None, num_segments=None):
     """
     :param source_index: index of source node (of edge) or source graph (of node)
     :param score: 1-D Array
     :param k: Keep top k targets for each source
     :param ratio: Keep num_targets * ratio targets for each source
+    :param num_segments: (not in the reference; asap() passes the graph count it has cached) a bound above every source id,
+        max(source_index) + 1 or more; given, the largest id is not read back from the device.  A value that is too small
+        is not silently used: the kernel validates every id against it and the call raises TfgxError (TFGX_ERR_INDEX).
+        None (the default) is the behaviour of every earlier release.
     :return: positions (into source_index / score) of the kept targets: sources ascending, scores descending,
         ties in input order.  ratio > 1 keeps every target (the reference would index its padding columns there).
     """
@@ -31,7 +35,7 @@ def topk_pool(source_index, score, k=None, ratio=None):
     if n == 0:
         out = torch.zeros(0, dtype=torch.int32, device=dev)
         return out.cpu().numpy() if as_np else out
-    num_segments = int(seg.max().item()) + 1
+    num_segments = int(seg.max().item()) + 1 if num_segments is None else int(num_segments)
     out_index = torch.empty(n, dtype=torch.int32, device=dev)
     out_count = torch.zeros(1, dtype=torch.int32, device=dev)
     ws_bytes = lib.tfgx_segment_topk_workspace_bytes(n, num_segments)

@@ -341,3 +341,30 @@ def reindex_sampled_edge_index(sampled_edge_index, sampled_node_index):
     out = table[ei.long().clamp(min=0)]
     out = torch.where(ei < 0, torch.full_like(out, -1), out)
     return _out(out, as_np)
+
+
+def convert_dense_adj_to_edge(dense_adj):
+    """The entries != 0.0 of a dense [n, n] adjacency as (edge_index int32 [2, nnz], edge_weight [nnz]) in row-major order
+    (reference: utils/graph_utils.py:272-284).  numpy in -> numpy out; runs in torch on the device."""
+    as_np = not isinstance(dense_adj, torch.Tensor)
+    adj = L.as_f32(dense_adj)
+    idx = torch.nonzero(adj != 0.0)                      # row-major
+    edge_index = idx.t().to(torch.int32).contiguous()
+    edge_weight = adj[idx[:, 0], idx[:, 1]]
+    return _out(edge_index, as_np), _out(edge_weight, as_np)
+
+
+def convert_dense_assign_to_edge(dense_assign, node_graph_index=None, num_nodes=None, num_clusters=None):
+    """A dense assignment [num_nodes, num_clusters] as (edge_index int32 [2, num_nodes * num_clusters] = [node; cluster],
+    edge_weight): EVERY entry, zeros included, in row-major order (reference: utils/graph_utils.py:287-322).  With
+    node_graph_index, column j of node i is cluster num_clusters * node_graph_index[i] + j.  numpy in -> numpy out."""
+    as_np = not isinstance(dense_assign, torch.Tensor)
+    s = L.as_f32(dense_assign)
+    n = int(s.shape[0]) if num_nodes is None else int(num_nodes)
+    kc = int(s.shape[1]) if num_clusters is None else int(num_clusters)
+    row = torch.arange(n, dtype=torch.int32, device=s.device).unsqueeze(1).expand(n, kc)
+    col = torch.arange(kc, dtype=torch.int32, device=s.device).unsqueeze(0).expand(n, kc)
+    if node_graph_index is not None:
+        col = col + L.as_i32(node_graph_index, s.device).reshape(-1, 1) * kc
+    edge_index = torch.stack([row.reshape(-1), col.reshape(-1)]).contiguous()
+    return _out(edge_index, as_np), _out(s.reshape(-1), as_np)
