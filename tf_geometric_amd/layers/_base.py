@@ -59,10 +59,13 @@ class Layer(object):
             # the layer OWNS its weights: a caller's float32 device tensor is copied, never aliased (an optimizer step
             # or requires_grad_ must not write into user data)
             t = L.as_f32(v).detach().clone().contiguous()
-            if self._trainable:
-                t.requires_grad_(True)
             name = k if k in self._weights else next((n for n, val in self._weights.items()
                                                       if val is getattr(self, attr)), k)
+            old = self._weights.get(name)
+            if old is not None and old.dim() == 0 and t.numel() == 1:
+                t = t.reshape(())                # a scalar weight (GIN's eps) stays one: a numpy scalar arrives as shape [1]
+            if self._trainable:
+                t.requires_grad_(True)
             setattr(self, attr, t)
             self._weights[name] = t
 

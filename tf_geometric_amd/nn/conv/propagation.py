@@ -21,7 +21,7 @@ CACHE_KEY_CHEBYNET_NORMED_EDGE_TEMPLATE = "chebynet_normed_edge_{}"
 
 
 def _prop(plan, h, w_csr, self_coef):
-    if AG.needs_grad(h):
+    if AG.needs_grad(h, w_csr):
         return AG.aggregate(plan, h, L.SUM, w_csr, self_coef)
     # k-hop chains gather narrow / odd-width rows (class scores: 7, 40, 47 ...) again and again: keep every link of the
     # chain on a line-friendly row stride (plan.gather_friendly_ld: F = 47 gathers 15 % faster at stride 48)
@@ -61,7 +61,16 @@ def _finish(h, bias, activation):
     return h if h.is_contiguous() else h.contiguous()
 
 
+def _refuse_trainable_edge_weight(edge_weight, what):
+    """The normalisations (gcn_norm_adj, chebynet_norm_edge) are raw kernel launches: a tracked edge_weight would get no
+    gradient from them.  Checked before any cache lookup, so a cached adjacency cannot hide it."""
+    if AG.needs_grad(edge_weight):
+        raise NotImplementedError("{}: an edge_weight that requires grad is not supported (the normalisation is not "
+                                  "differentiable here); detach it or call under torch.no_grad()".format(what))
+
+
 def _normed(x, edge_index, edge_weight, cache, **norm_kwargs):
+    _refuse_trainable_edge_weight(edge_weight, "gcn_norm_adj of a propagation conv")
     n = int(x.shape[0])
     key = "tfgx_gcn_adj"
     adj = cache.get(key) if cache is not None else None
@@ -187,6 +196,8 @@ def le_conv(x, edge_index, edge_weight, self_kernel, self_bias, aggr_self_kernel
     plan = CsrPlan.from_cache(edge_index, n, n, cache)
     if edge_weight is None:
         w_csr = None                                                   # ones (:21-22)
+    elif AG.needs_grad(edge_weight):
+        w_csr = AG.edge_attr_csr(plan, edge_weight)                    # trainable weights: a differentiable permutation
     else:
         w_csr = plan.edge_attr_to_csr(edge_weight)
     self_h = _dense(x, self_kernel, self_bias)
@@ -201,6 +212,7 @@ def chebynet_norm_edge(edge_index, num_nodes, edge_weight=None, normalization_ty
     self-loops removed, sym: D^-1/2 A D^-1/2 + I, rw: D^-1 A + I, None: (deg_r - w) on edges and on an appended
     unit self-loop; everything times 2 / lambda_max (lambda_max = 2, or the Laplacian's largest eigenvalue when
     use_dynamic_lambda_max: laplacian_max_eigenvalue)."""
+    _refuse_trainable_edge_weight(edge_weight, "chebynet_norm_edge")
     if cache is not None:
         key = CACHE_KEY_CHEBYNET_NORMED_EDGE_TEMPLATE.format(normalization_type)
         if cache.get(key) is not None:
