@@ -254,3 +254,111 @@ def test_fused_h16_layers_training(tfg, oracle, kind, dtype):
         plan = P.CsrPlan.build(ei, n, n)
         with pytest.raises(NotImplementedError):
             AG.aggregate_project(plan, hq, tfg._lib.SUM, layer.kernel, plan.edge_attr_to_csr(w).clone().requires_grad_(True))
+
+
+# --------------------------------------------------------------------------------- the 16-bit and float32 routes, case by case
+_TWIN_ENTRIES = ("aggregate", "aggregate_project", "sage_wide")
+_TWIN_N, _TWIN_F, _TWIN_UNITS, _TWIN_E = 70, 100, 256, 800      # one full 64-row tile plus a remainder
+
+
+def twin_cases(entry):
+    """bias x ReLU x kernel(s) trainable x table's source trainable x mean x (aggregate, aggregate_project) trainable self_coef;
+    `aggregate` has no kernel, and takes one rectangular case more (n_dst = 1 < n_src with a self_coef)."""
+    import itertools
+    for bias, relu, k_grad, t_grad, mean, self_ in itertools.product((False, True), repeat=6):
+        if (entry == "aggregate" and k_grad) or (entry == "sage_wide" and self_):
+            continue
+        yield dict(bias=bias, relu=relu, k_grad=k_grad, t_grad=t_grad, mean=mean, self=self_, n_dst=_TWIN_N)
+    if entry == "aggregate":
+        yield dict(bias=True, relu=True, k_grad=False, t_grad=True, mean=True, self=True, n_dst=1)
+
+
+def twin_graph(tfg, n_dst):
+    """(plan [n_dst x _TWIN_N], constant edge weights in CSR order)."""
+    from tf_geometric_amd import plan as P
+    rng = _rng(32100, n_dst)
+    E = _TWIN_E if n_dst > 1 else 23
+    ei = np.stack([rng.integers(0, n_dst, size=E), rng.integers(0, _TWIN_N, size=E)]).astype(np.int32)
+    plan = P.CsrPlan.build(tfg._lib.as_i32(ei), n_dst, _TWIN_N)
+    return plan, plan.edge_attr_to_csr(rng.uniform(0.2, 1.5, size=E).astype(np.float32))
+
+
+def twin_run(tfg, entry, c, plan, w_csr, t, G, half):
+    """One public entry point of autograd.py on HalfRows.from_tensor(t) (half) or on t.float(), same weights, same upstream
+    gradient -> (forward, {name: gradient}, (fused launches, with side output, fused launches over a 16-bit table))."""
+    from tf_geometric_amd import plan as P, autograd as AG
+    L = tfg._lib
+    rng = _rng(32101, 0)
+
+    def leaf(a, grad):
+        return torch.from_numpy(np.asarray(a, dtype=np.float32)).cuda().requires_grad_(grad)
+    F = int(t.shape[1])
+    src = (t.detach().clone() if half else t.detach().float()).requires_grad_(c["t_grad"])
+    x = P.HalfRows.from_tensor(src) if half else src
+    op, act = (L.MEAN if c["mean"] else L.SUM), (L.ACT_RELU if c["relu"] else L.ACT_NONE)
+    ku = _TWIN_UNITS // 2
+    leaves = {"source": src}
+    if entry == "aggregate_project":
+        leaves["kernel"] = leaf(rng.standard_normal((F, _TWIN_UNITS)) / F ** 0.5, c["k_grad"])
+    elif entry == "sage_wide":
+        leaves["self_kernel"] = leaf(rng.standard_normal((F, ku)) / F ** 0.5, c["k_grad"])
+        leaves["neighbor_kernel"] = leaf(rng.standard_normal((F, ku)) / F ** 0.5, c["k_grad"])
+    if c["bias"]:
+        leaves["bias"] = leaf(rng.standard_normal(F if entry == "aggregate" else _TWIN_UNITS) * 0.3, True)
+    if c["self"]:
+        leaves["self_coef"] = leaf(rng.uniform(0.1, 1.0, size=plan.n_dst), True)
+    bias, sc = leaves.get("bias"), leaves.get("self_coef")
+    before = (P.FUSED_STATS["launches"], P.FUSED_STATS["with_side_output"], P.FUSED_H16_STATS["launches"])
+    if entry == "aggregate":
+        out = AG.aggregate(plan, x, op, w_csr, sc, bias=bias, act=act)
+    elif entry == "aggregate_project":
+        assert P.aggregate_gemm_applies(x, leaves["kernel"], op)
+        out = AG.aggregate_project(plan, x, op, leaves["kernel"], w_csr, sc, bias, act)
+    else:
+        assert P.aggregate_gemm_applies(x, leaves["neighbor_kernel"], op)
+        out = AG.sage_wide(plan, op, x, leaves["self_kernel"], leaves["neighbor_kernel"], w_csr, bias, act)
+    stats = (P.FUSED_STATS["launches"] - before[0], P.FUSED_STATS["with_side_output"] - before[1],
+             P.FUSED_H16_STATS["launches"] - before[2])
+    assert out is not None and out.requires_grad == any(v.requires_grad for v in leaves.values())
+    if out.requires_grad:
+        out.backward(G)
+    return out.detach(), {k: v.grad for k, v in leaves.items() if v.requires_grad}, stats
+
+
+def twin_inputs(tfg, entry, dtype):
+    """(16-bit table values [n, F], {n_dst: (plan, w_csr, upstream gradient)}) of one (entry point, dtype)."""
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(32102)
+    t = torch.randn(_TWIN_N, _TWIN_F, generator=gen, device="cuda").to(dtype)
+    graphs = {}
+    for n_dst in sorted({c["n_dst"] for c in twin_cases(entry)}):
+        G = torch.randn(n_dst, _TWIN_F if entry == "aggregate" else _TWIN_UNITS, generator=gen, device="cuda")
+        graphs[n_dst] = twin_graph(tfg, n_dst) + (G,)
+    return t, graphs
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("entry", _TWIN_ENTRIES)
+def test_fused_h16_route_equals_float32_route(tfg, entry, dtype):
+    """autograd.aggregate / aggregate_project / sage_wide on HalfRows.from_tensor(t) against the same call on t.float(), over
+    every combination of twin_cases: the forward and every float32 gradient (kernels, bias, self_coef) torch.equal, d/dt the
+    float32 route's d/dx rounded once to t.dtype (bit for bit), one fused launch per call on either route (none for aggregate)
+    with the aggregate written beside it exactly when the kernel's gradient is wanted."""
+    t, graphs = twin_inputs(tfg, entry, dtype)
+    for c in twin_cases(entry):
+        what = "{} {} {}".format(entry, dtype, " ".join("{}={}".format(k, int(v)) for k, v in c.items()))
+        plan, w_csr, G = graphs[c["n_dst"]]
+        out_h, grads_h, stats_h = twin_run(tfg, entry, c, plan, w_csr, t, G, True)
+        out_f, grads_f, stats_f = twin_run(tfg, entry, c, plan, w_csr, t, G, False)
+        fused = int(entry != "aggregate")
+        assert stats_h == (fused, int(fused and c["k_grad"]), fused), what + ": launches over the 16-bit table"
+        assert stats_f == (fused, int(fused and c["k_grad"]), 0), what + ": launches over the float32 table"
+        assert out_h.dtype == torch.float32 and torch.equal(out_h, out_f), what + ": forward"
+        assert sorted(grads_h) == sorted(grads_f), what
+        for k in grads_f:
+            assert grads_h[k] is not None and grads_f[k] is not None, what + ": no d/d" + k
+            if k == "source":
+                assert grads_h[k].dtype == dtype and grads_h[k].shape == t.shape, what
+                _same16(grads_h[k], grads_f[k].to(dtype), what + " d/dt vs the float32 route's d/dx rounded")
+            else:
+                assert torch.equal(grads_h[k], grads_f[k]), what + ": d/d" + k

@@ -7,6 +7,11 @@ C-ABI kernel launches:
 
   aggregate (sum / mean, weighted)  backward wrt x  = the forward kernel on the transposed (CSR-by-source) plan
                                     backward wrt w  = tfgx_sddmm_f32
+  aggregate_project, sage_wide      forward = ONE launch of tfgx_aggregate_gemm_f32 (+ the self half's GEMM); d/dkernel from the
+                                    aggregate written beside it (tfgx_gemm_tn_f32), d/d(aggregate) = g @ kernel^T, then as above
+    ... over a HalfRows (16-bit)    the SAME three Functions: the table is what the kernel reads (tfgx_segment_reduce_h16 /
+                                    tfgx_aggregate_gemm_h16, the float32 route's bits), the tensor autograd differentiates is the
+                                    table's float32 gradient sink (_HalfGradSink rounds the summed d/dx to the table's type once)
   aggregate (max)                   training forward saves (max, tie count, arg position); backward = per-edge winner masks +
                                     one gather per edge (tfgx_segment_max_backward_mask_f32, bit-reproducible; ties walked
                                     exactly, TF semantics); MAX_GRADIENT_MODE selects the atomics ("push") or two-gather ("pull") forms
@@ -112,15 +117,57 @@ def _aggregate_grad_x(plan, mean, g, w_csr, self_coef):
     return gx, g
 
 
+def _half_source(h, w_csr):
+    """(gradient target, edge weights as constants) for a HalfRows source: d/dx goes, in float32, to the table's gradient sink
+    (_HalfGradSink; None when the table's source wants no gradient), and the edge weights cannot train."""
+    if needs_grad(w_csr):
+        raise NotImplementedError("edge weights that require grad are not supported over a 16-bit table (the SDDMM is float32-only)")
+    return _half_grad_proxy(h), None if w_csr is None else w_csr.detach()
+
+
+def _behind_relu(g, out, act, agg=None, upstream=True):
+    """(the gradient behind the layer's ReLU, gate): one masked copy of g (tfgx_relu_backward_f32), gate None — or, in layer 0
+    of the aggregate -> project operators (nothing upstream wants a gradient, the aggregate was kept for the kernel's), g itself
+    and gate = the layer's output: the weight-gradient reductions apply the mask themselves and the masked gradient is never
+    written — one 3 x [N, units] pass less (1.45 ms at products shape; the gated kernel costs 0.05 ms more than the plain one
+    since its operands moved to raw buffer loads)."""
+    gated = act == L.ACT_RELU and agg is not None and not upstream and GATED_AGGREGATE_PROJECT
+    if act == L.ACT_RELU and not gated:
+        return relu_backward(g, out), None
+    return g.contiguous(), (out if gated else None)
+
+
+def _projection_grads(agg, g, want_b, gate=None):
+    """(d/dkernel, d/dbias) of aggregate @ kernel + bias given g: ONE reduction over the node dimension on the saved aggregate
+    (agg: kept exactly when the kernel wants its gradient), else the bias' column sums alone."""
+    if agg is not None:
+        return gemm_tn(agg, g, want_bias=want_b, gate=gate)
+    return None, (column_sums(g) if want_b else None)
+
+
+def _source_grads(plan, mean, x, table, w_csr, self_coef, g, need_x, need_w, need_s, kernel=None):
+    """_aggregate_backward for the operators below.  kernel: g is d/d(aggregate @ kernel), so d/d(aggregate) = g @ kernel^T
+    first.  The float32 values of the source rows (the SDDMM, the self-loop coefficient's gradient) are x, or a 16-bit table
+    widened — only when one of the two is wanted."""
+    if kernel is not None:
+        g = gemm_bias_act(g, transpose(kernel.detach()))
+    if isinstance(table, HalfRows):
+        wanted = (need_w and w_csr is not None) or (need_s and self_coef is not None)
+        x = table.float() if wanted else None
+    return _aggregate_backward(plan, mean, x, w_csr, self_coef, g, need_x, need_w, need_s)
+
+
 class _Aggregate(torch.autograd.Function):
     """out = act( (1/cnt[r]) * ( sum_{i in row r} w[i] x[col[i]] + self_coef[r] x[r] ) + bias )   (cnt only for mean);
     bias and activation ride in the kernel's epilogue, the ReLU's backward is one masked copy of the gradient."""
 
     @staticmethod
-    def forward(ctx, plan, mean, x, w_csr, self_coef, rows=None, bias=None, act=L.ACT_NONE):
-        """`rows`: x in another source layout (plan.static_rows) — same values, same result bits."""
-        ctx.plan, ctx.mean, ctx.act = plan, mean, act
-        out = segment_reduce(plan, x.detach() if rows is None else rows, L.MEAN if mean else L.SUM,
+    def forward(ctx, plan, mean, x, w_csr, self_coef, table=None, bias=None, act=L.ACT_NONE):
+        """x: the tensor d/dx goes to.  `table`: what the kernel reads when that is not x itself — x in another source layout
+        (a SplitRows: plan.static_rows), or a HalfRows, whose gradient sink x then is (_half_source; tfgx_segment_reduce_h16) —
+        same values, same result bits."""
+        ctx.plan, ctx.mean, ctx.act, ctx.table = plan, mean, act, table
+        out = segment_reduce(plan, x.detach() if table is None else table, L.MEAN if mean else L.SUM,
                              w_csr=None if w_csr is None else w_csr.detach(),
                              self_coef=None if self_coef is None else self_coef.detach(),
                              bias=None if bias is None else bias.detach().contiguous(), act=act)
@@ -129,12 +176,11 @@ class _Aggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        plan = ctx.plan
         x, w_csr, self_coef, bias, out = ctx.saved_tensors
-        g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
-        gb = column_sums(g) if (bias is not None and ctx.needs_input_grad[6]) else None
-        gx, gw, gs = _aggregate_backward(plan, ctx.mean, x, w_csr, self_coef, g, ctx.needs_input_grad[2],
-                                         ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+        _, _, need_x, need_w, need_s, _, need_b, _ = ctx.needs_input_grad
+        g, _ = _behind_relu(g, out, ctx.act)
+        _, gb = _projection_grads(None, g, bias is not None and need_b)
+        gx, gw, gs = _source_grads(ctx.plan, ctx.mean, x, ctx.table, w_csr, self_coef, g, need_x, need_w, need_s)
         return None, None, gx, gw, gs, None, gb, None
 
 
@@ -163,50 +209,36 @@ def _aggregate_backward(plan, mean, x, w_csr, self_coef, g, need_x, need_w, need
 
 class _AggregateProject(torch.autograd.Function):
     """out = act( reduce(plan, x, w, self_coef) @ kernel + bias ) — the aggregate-then-project layers (GCN with units > F,
-    the neighbour half of mean / sum GraphSAGE) in ONE forward launch (tfgx_aggregate_gemm_f32).  When the kernel needs a
-    gradient the launch also writes the aggregate itself (side output: d/dkernel = aggregate^T @ g); the projection still
-    reads it from LDS, so the training forward saves the GEMM's read-back of the [N, F] aggregate."""
+    the neighbour half of mean / sum GraphSAGE) in ONE forward launch (tfgx_aggregate_gemm_f32; tfgx_aggregate_gemm_h16 over a
+    HalfRows: the same bits).  When the kernel needs a gradient the launch also writes the aggregate itself (side output:
+    d/dkernel = aggregate^T @ g); the projection still reads it from LDS, so the training forward saves the GEMM's read-back of
+    the [N, F] aggregate."""
 
     @staticmethod
-    def forward(ctx, plan, mean, x, w_csr, self_coef, kernel, bias, act, rows=None):
-        """`rows`: x in the static feature layout (plan.static_rows) — same values, same aggregate bits."""
-        n, F = plan.n_dst, int(x.shape[1])
+    def forward(ctx, plan, mean, x, w_csr, self_coef, kernel, bias, act, table=None):
+        """x, `table`: as in _Aggregate.forward (a SplitRows: same values, same aggregate bits)."""
         need_agg = ctx.needs_input_grad[5]
-        agg = torch.empty((n, F), dtype=torch.float32, device=x.device) if need_agg else None
-        out = aggregate_gemm(plan, x.detach() if rows is None else rows, L.MEAN if mean else L.SUM, kernel.detach(),
+        agg = torch.empty((plan.n_dst, int(kernel.shape[0])), dtype=torch.float32, device=kernel.device) if need_agg else None
+        out = aggregate_gemm(plan, x.detach() if table is None else table, L.MEAN if mean else L.SUM, kernel.detach(),
                              w_csr=None if w_csr is None else w_csr.detach(),
                              self_coef=None if self_coef is None else self_coef.detach(),
-                             bias=None if bias is None else bias.detach(), act=act, agg_out=agg)
+                             bias=None if bias is None else bias.detach(), act=act, agg_out=agg, training=True)
         if out is None:
             raise L.TfgxError("_AggregateProject: the fused launch declined (ask plan.aggregate_gemm_applies first)")
-        ctx.plan, ctx.mean, ctx.act = plan, mean, act
+        ctx.plan, ctx.mean, ctx.act, ctx.table = plan, mean, act, table
         ctx.save_for_backward(x, w_csr, self_coef, kernel, bias, agg, out if act == L.ACT_RELU else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w_csr, self_coef, kernel, bias, agg, out = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want_b = bias is not None and need[6]
-        # layer 0 (nothing upstream wants a gradient): the ReLU mask is applied INSIDE the weight-gradient reduction (gate = the
-        # layer's output) and the masked gradient is never written — one 3 x [N, units] pass less (1.45 ms at products shape;
-        # the gated kernel costs 0.05 ms more than the plain one since its operands moved to raw buffer loads)
-        gated = (ctx.act == L.ACT_RELU and agg is not None and (need[5] or want_b)
-                 and not (need[2] or need[3] or need[4]) and GATED_AGGREGATE_PROJECT)
-        if not gated:
-            g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
-        gk = gb = None
-        if need[5] or want_b:
-            if agg is not None:
-                gk, gb = gemm_tn(agg, g.contiguous() if gated else g, want_bias=want_b, gate=out if gated else None)
-                if not need[5]:
-                    gk = None
-            else:
-                gb = column_sums(g)
+        _, _, need_x, need_w, need_s, _, need_b, _, _ = ctx.needs_input_grad
+        upstream = need_x or need_w or need_s
+        g, gate = _behind_relu(g, out, ctx.act, agg, upstream)
+        gk, gb = _projection_grads(agg, g, bias is not None and need_b, gate)
         gx = gw = gs = None
-        if need[2] or need[3] or need[4]:
-            g_agg = gemm_bias_act(g, transpose(kernel.detach()))          # d/d(aggregate) = g @ kernel^T
-            gx, gw, gs = _aggregate_backward(ctx.plan, ctx.mean, x, w_csr, self_coef, g_agg, need[2], need[3], need[4])
+        if upstream:
+            gx, gw, gs = _source_grads(ctx.plan, ctx.mean, x, ctx.table, w_csr, self_coef, g, need_x, need_w, need_s, kernel)
         return None, None, gx, gw, gs, gk, gb, None, None
 
 
@@ -214,73 +246,69 @@ def aggregate_project(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None
     """Differentiable act(reduce(plan, x) @ kernel + bias) on the fused launch, or None when it does not take the shape
     (the caller then composes aggregate + linear).  rows: x's static layout (plan.static_rows) or None / x itself.
     x may be a HalfRows (tfgx_aggregate_gemm_h16; rows is not consulted; trainable edge weights: NotImplementedError)."""
-    if isinstance(x, HalfRows):
-        return _aggregate_project_half(plan, x, op, kernel, w_csr, self_coef, bias, act)
-    rows = rows if isinstance(rows, SplitRows) else None
-    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if rows is None else rows, kernel, op):
+    table = x if isinstance(x, HalfRows) else (rows if isinstance(rows, SplitRows) else None)
+    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if table is None else table, kernel, op):
         return None
+    if table is x:
+        x, w_csr = _half_source(x, w_csr)
     return _AggregateProject.apply(plan, op == L.MEAN, x, w_csr, self_coef, L.as_f32(kernel),
-                                   None if bias is None else L.as_f32(bias), act, rows)
+                                   None if bias is None else L.as_f32(bias), act, table)
 
 
 class _SageWide(torch.autograd.Function):
-    """h = act([x @ ks | reduce(w * x[col]) @ kn] + bias): mean / sum GraphSAGE, concat form, aggregation first (ku >= F:
+    """h = act([xs @ ks | reduce(w * x[col]) @ kn] + bias): mean / sum GraphSAGE, concat form, aggregation first (ku >= F:
     nn/conv/graph_sage.py:34-58 with demo_graph_sage.py:29-30's units=256).  The neighbour half is ONE launch
-    (tfgx_aggregate_gemm_f32 straight into its half of h, aggregate written beside it for d/dkn), the self half the GEMM."""
+    (tfgx_aggregate_gemm_f32 / _h16 straight into its half of h, aggregate written beside it for d/dkn), the self half the GEMM."""
 
     @staticmethod
-    def forward(ctx, plan, mean, x, ks, kn, w_csr, bias, act, rows=None):
-        n, F, na, nb = int(x.shape[0]), int(x.shape[1]), int(ks.shape[1]), int(kn.shape[1])
-        h = torch.empty((n, na + nb), dtype=torch.float32, device=x.device)
+    def forward(ctx, plan, mean, x, xs, ks, kn, w_csr, bias, act, table=None):
+        """x, `table`: as in _Aggregate.forward.  xs: what the self half reads — x itself, or over a HalfRows the widened
+        table (widen), whose gradient reaches the same sink: the two halves' d/dx are summed by autograd either way."""
+        n, F, na, nb = int(xs.shape[0]), int(kn.shape[0]), int(ks.shape[1]), int(kn.shape[1])
+        h = torch.empty((n, na + nb), dtype=torch.float32, device=xs.device)
         bd = None if bias is None else bias.detach().contiguous()
-        agg = torch.empty((n, F), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[4] else None
-        got = aggregate_gemm(plan, x.detach() if rows is None else rows, L.MEAN if mean else L.SUM, kn.detach(),
+        agg = torch.empty((n, F), dtype=torch.float32, device=xs.device) if ctx.needs_input_grad[5] else None
+        got = aggregate_gemm(plan, x.detach() if table is None else table, L.MEAN if mean else L.SUM, kn.detach(),
                              w_csr=None if w_csr is None else w_csr.detach(),
-                             bias=None if bd is None else bd[na:].contiguous(), act=act, out=h[:, na:], agg_out=agg)
+                             bias=None if bd is None else bd[na:].contiguous(), act=act, out=h[:, na:], agg_out=agg, training=True)
         if got is None:
             raise L.TfgxError("_SageWide: the fused launch declined (ask plan.aggregate_gemm_applies first)")
-        gemm_bias_act(x.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
-        ctx.plan, ctx.mean, ctx.act, ctx.na = plan, mean, act, na
-        ctx.save_for_backward(x, ks, kn, w_csr, bias, agg, h if act == L.ACT_RELU else None)
+        gemm_bias_act(xs.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
+        ctx.plan, ctx.mean, ctx.act, ctx.na, ctx.table = plan, mean, act, na, table
+        ctx.save_for_backward(xs, ks, kn, w_csr, bias, agg, h if act == L.ACT_RELU else None)
         return h
 
     @staticmethod
     def backward(ctx, g):
-        x, ks, kn, w_csr, bias, agg, h = ctx.saved_tensors
-        plan, na, need = ctx.plan, ctx.na, ctx.needs_input_grad
-        want_b = bias is not None and need[6]
-        # layer 0 (x carries no gradient): both weight-gradient reductions apply the ReLU mask themselves (see _AggregateProject)
-        gated = ctx.act == L.ACT_RELU and not need[2] and agg is not None and GATED_AGGREGATE_PROJECT
-        g = g.contiguous() if (gated or ctx.act != L.ACT_RELU) else relu_backward(g, h)
+        xs, ks, kn, w_csr, bias, agg, h = ctx.saved_tensors
+        _, _, need_x, need_xs, need_ks, _, _, need_b, _, _ = ctx.needs_input_grad
+        na, upstream, want_b = ctx.na, need_x or need_xs, bias is not None and need_b
+        g, gate = _behind_relu(g, h, ctx.act, agg, upstream)          # gated: layer 0, x carries no gradient
         gs, gn = g[:, :na], g[:, na:]
-        gx, gks, gba = _linear_grads(x, ks, gs, need[2], need[3], want_b, gate=h[:, :na] if gated else None)
-        gkn = gbb = None
-        if need[4] or want_b:
-            if agg is not None:
-                gkn, gbb = gemm_tn(agg, gn, want_bias=want_b, gate=h[:, na:] if gated else None)
-                if not need[4]:
-                    gkn = None
-            else:
-                gbb = column_sums(gn)
-        if need[2]:
-            g_agg = gemm_bias_act(gn, transpose(kn.detach()))
-            gx2, _, _ = _aggregate_backward(plan, ctx.mean, x, w_csr, None, g_agg, True, False, False)
-            gx = gx + gx2
+        gxs, gks, gba = _linear_grads(xs, ks, gs, upstream, need_ks, want_b, gate=None if gate is None else gate[:, :na])
+        gkn, gbb = _projection_grads(agg, gn, want_b, None if gate is None else gate[:, na:])
+        gx = None
+        if upstream:
+            gx, _, _ = _source_grads(ctx.plan, ctx.mean, None, ctx.table, w_csr, None, gn, True, False, False, kn)
         gb = torch.cat([gba, gbb]) if want_b else None
-        return None, None, gx, gks, gkn, None, gb, None, None
+        return None, None, gx if need_x else None, gxs if need_xs else None, gks, gkn, None, gb, None, None
 
 
 def sage_wide(plan, op, x, ks, kn, w_csr=None, bias=None, act=L.ACT_NONE, rows=None):
     """Differentiable mean / sum GraphSAGE layer body (concat form, aggregation first) with the neighbour half on the fused
     launch, or None when it does not take the shape.  Edge weights are constants here (trainable ones take the un-fused route).
-    rows: x's static layout (plan.static_rows) or None / x itself."""
-    if isinstance(x, HalfRows):
-        return _sage_wide_half(plan, op, x, ks, kn, w_csr, bias, act)
-    rows = rows if isinstance(rows, SplitRows) else None
-    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if rows is None else rows, kn, op):
+    rows: x's static layout (plan.static_rows) or None / x itself.
+    x may be a HalfRows (rows is not consulted; the self half reads the widened table; trainable edge weights:
+    NotImplementedError)."""
+    table = x if isinstance(x, HalfRows) else (rows if isinstance(rows, SplitRows) else None)
+    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if table is None else table, kn, op):
         return None
-    return _SageWide.apply(plan, op == L.MEAN, x, L.as_f32(ks), L.as_f32(kn), w_csr,
-                           None if bias is None else L.as_f32(bias), act, rows)
+    xs = x
+    if table is x:
+        x, w_csr = _half_source(table, w_csr)
+        xs = widen(table)
+    return _SageWide.apply(plan, op == L.MEAN, x, xs, L.as_f32(ks), L.as_f32(kn), w_csr,
+                           None if bias is None else L.as_f32(bias), act, table)
 
 
 # Gradient of max aggregation (tf.math.unsorted_segment_max, ties share evenly):
@@ -571,168 +599,35 @@ def widen(h):
     return h.float() if proxy is None else _WidenHalf.apply(h, proxy)
 
 
-class _AggregateHalf(torch.autograd.Function):
-    """_Aggregate over a HalfRows (16-bit storage): the forward is tfgx_segment_reduce_h16 — the float32 route's bits —, the
-    backward the existing float32 kernels on the float32 gradient; d/dx goes, in float32, to the table's gradient sink
-    (_HalfGradSink), which rounds to the table's type as the last step."""
-
-    @staticmethod
-    def forward(ctx, plan, mean, h, proxy, w_csr, self_coef, bias, act):
-        ctx.plan, ctx.mean, ctx.act, ctx.h = plan, mean, act, h
-        out = segment_reduce(plan, h, L.MEAN if mean else L.SUM, w_csr=w_csr,
-                             self_coef=None if self_coef is None else self_coef.detach(),
-                             bias=None if bias is None else bias.detach().contiguous(), act=act)
-        ctx.save_for_backward(w_csr, self_coef, bias, out if act == L.ACT_RELU else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        plan, h = ctx.plan, ctx.h
-        w_csr, self_coef, bias, out = ctx.saved_tensors
-        g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
-        gb = column_sums(g) if (bias is not None and ctx.needs_input_grad[6]) else None
-        need_x, need_s = ctx.needs_input_grad[3], ctx.needs_input_grad[5] and self_coef is not None
-        gx32, _, gs = _aggregate_backward(plan, ctx.mean, h.float() if need_s else None, w_csr, self_coef, g, need_x, False, need_s)
-        return None, None, None, gx32 if need_x else None, None, gs, gb, None
-
-
-def _refuse_trainable_weights_half(w_csr):
-    if isinstance(w_csr, torch.Tensor) and w_csr.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("edge weights that require grad are not supported over a 16-bit table (the SDDMM is float32-only)")
-
-
-class _AggregateProjectHalf(torch.autograd.Function):
-    """_AggregateProject over a HalfRows: the forward is ONE launch of tfgx_aggregate_gemm_h16 (the float32 route's bits, the
-    float32 aggregate written beside it when the kernel wants a gradient), the backward the existing float32 kernels; d/dx goes,
-    in float32, to the table's gradient sink (_HalfGradSink), as in _AggregateHalf."""
-
-    @staticmethod
-    def forward(ctx, plan, mean, h, proxy, w_csr, self_coef, kernel, bias, act):
-        agg = torch.empty((plan.n_dst, h.F), dtype=torch.float32, device=h.device) if ctx.needs_input_grad[6] else None
-        out = aggregate_gemm(plan, h, L.MEAN if mean else L.SUM, kernel.detach(), w_csr=w_csr,
-                             self_coef=None if self_coef is None else self_coef.detach(),
-                             bias=None if bias is None else bias.detach(), act=act, agg_out=agg, training=True)
-        if out is None:
-            raise L.TfgxError("_AggregateProjectHalf: the fused launch declined (ask plan.aggregate_gemm_applies first)")
-        ctx.plan, ctx.mean, ctx.act, ctx.h = plan, mean, act, h
-        ctx.save_for_backward(w_csr, self_coef, kernel, bias, agg, out if act == L.ACT_RELU else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        w_csr, self_coef, kernel, bias, agg, out = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want_b = bias is not None and need[7]
-        need_x, need_s = need[3], need[5] and self_coef is not None
-        gated = (ctx.act == L.ACT_RELU and agg is not None and (need[6] or want_b) and not (need_x or need_s)
-                 and GATED_AGGREGATE_PROJECT)
-        if not gated:
-            g = relu_backward(g, out) if ctx.act == L.ACT_RELU else g.contiguous()
-        gk = gb = None
-        if need[6] or want_b:
-            if agg is not None:
-                gk, gb = gemm_tn(agg, g.contiguous() if gated else g, want_bias=want_b, gate=out if gated else None)
-                if not need[6]:
-                    gk = None
-            else:
-                gb = column_sums(g)
-        gx = gs = None
-        if need_x or need_s:
-            g_agg = gemm_bias_act(g, transpose(kernel.detach()))          # d/d(aggregate) = g @ kernel^T
-            gx, _, gs = _aggregate_backward(ctx.plan, ctx.mean, ctx.h.float() if need_s else None, w_csr, self_coef, g_agg,
-                                            need_x, False, need_s)
-        return None, None, None, gx if need_x else None, None, gs, gk, gb, None
-
-
-def _aggregate_project_half(plan, h, op, kernel, w_csr, self_coef, bias, act):
-    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(h, kernel, op):
-        return None
-    _refuse_trainable_weights_half(w_csr)
-    return _AggregateProjectHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), None if w_csr is None else w_csr.detach(),
-                                       self_coef, L.as_f32(kernel), None if bias is None else L.as_f32(bias), act)
-
-
-class _SageWideHalf(torch.autograd.Function):
-    """_SageWide over a HalfRows: the neighbour half is ONE launch of tfgx_aggregate_gemm_h16 straight into its half of h, the
-    self half the float32 GEMM on the widened table xw = widen(h).  d/dx of the neighbour half goes to the table's gradient
-    sink, that of the self half to xw (which leads to the same sink): summed in float32, rounded once."""
-
-    @staticmethod
-    def forward(ctx, plan, mean, hrows, proxy, xw, ks, kn, w_csr, bias, act):
-        n, F, na, nb = hrows.shape[0], hrows.F, int(ks.shape[1]), int(kn.shape[1])
-        h = torch.empty((n, na + nb), dtype=torch.float32, device=hrows.device)
-        bd = None if bias is None else bias.detach().contiguous()
-        agg = torch.empty((n, F), dtype=torch.float32, device=hrows.device) if ctx.needs_input_grad[6] else None
-        got = aggregate_gemm(plan, hrows, L.MEAN if mean else L.SUM, kn.detach(), w_csr=w_csr,
-                             bias=None if bd is None else bd[na:].contiguous(), act=act, out=h[:, na:], agg_out=agg, training=True)
-        if got is None:
-            raise L.TfgxError("_SageWideHalf: the fused launch declined (ask plan.aggregate_gemm_applies first)")
-        gemm_bias_act(xw.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
-        ctx.plan, ctx.mean, ctx.act, ctx.na = plan, mean, act, na
-        ctx.save_for_backward(xw, ks, kn, w_csr, bias, agg, h if act == L.ACT_RELU else None)
-        return h
-
-    @staticmethod
-    def backward(ctx, g):
-        xw, ks, kn, w_csr, bias, agg, h = ctx.saved_tensors
-        plan, na, need = ctx.plan, ctx.na, ctx.needs_input_grad
-        want_b = bias is not None and need[8]
-        need_x = need[3] or need[4]
-        gated = ctx.act == L.ACT_RELU and not need_x and agg is not None and GATED_AGGREGATE_PROJECT
-        g = g.contiguous() if (gated or ctx.act != L.ACT_RELU) else relu_backward(g, h)
-        gs, gn = g[:, :na], g[:, na:]
-        gxw, gks, gba = _linear_grads(xw, ks, gs, need_x, need[5], want_b, gate=h[:, :na] if gated else None)
-        gkn = gbb = None
-        if need[6] or want_b:
-            if agg is not None:
-                gkn, gbb = gemm_tn(agg, gn, want_bias=want_b, gate=h[:, na:] if gated else None)
-                if not need[6]:
-                    gkn = None
-            else:
-                gbb = column_sums(gn)
-        gx = None
-        if need_x:
-            g_agg = gemm_bias_act(gn, transpose(kn.detach()))
-            gx, _, _ = _aggregate_backward(plan, ctx.mean, None, w_csr, None, g_agg, True, False, False)
-        gb = torch.cat([gba, gbb]) if want_b else None
-        return None, None, None, gx if need[3] else None, gxw if need[4] else None, gks, gkn, None, gb, None
-
-
-def _sage_wide_half(plan, op, h, ks, kn, w_csr, bias, act):
-    if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(h, kn, op):
-        return None
-    _refuse_trainable_weights_half(w_csr)
-    return _SageWideHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), widen(h), L.as_f32(ks), L.as_f32(kn),
-                               None if w_csr is None else w_csr.detach(), None if bias is None else L.as_f32(bias), act)
-
-
-def _aggregate_half(plan, h, op, w_csr, self_coef, bias, act, rows=None, max_passes=None):
+def _aggregate_half(plan, h, op, w_csr, self_coef, bias, act, rows, max_passes):
+    """What aggregate checks for a HalfRows; max aggregation (inference only) is answered here, sum / mean with None."""
     if rows is not None or max_passes is not None:
         raise TypeError("aggregate on a HalfRows takes neither rows= (the split-row layouts) nor max_passes= (the tracked max)")
-    if op == L.MAX:
-        if needs_grad(h, w_csr, self_coef, bias):
-            raise NotImplementedError("max aggregation over a 16-bit table is inference-only (the kernel keeps no track table)")
-        return segment_reduce(plan, h, L.MAX, w_csr=w_csr, self_coef=self_coef, bias=bias, act=act)
-    if isinstance(w_csr, torch.Tensor) and w_csr.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("edge weights that require grad are not supported over a 16-bit table (the SDDMM is float32-only)")
-    return _AggregateHalf.apply(plan, op == L.MEAN, h, _half_grad_proxy(h), None if w_csr is None else w_csr.detach(), self_coef,
-                                bias, act)
+    if op != L.MAX:
+        return None
+    if needs_grad(h, w_csr, self_coef, bias):
+        raise NotImplementedError("max aggregation over a 16-bit table is inference-only (the kernel keeps no track table)")
+    return segment_reduce(plan, h, L.MAX, w_csr=w_csr, self_coef=self_coef, bias=bias, act=act)
 
 
 def aggregate(plan, x, op, w_csr=None, self_coef=None, rows=None, bias=None, act=L.ACT_NONE, max_passes=None):
     """Differentiable gather-scale-segment-reduce (sum / mean / max) on `plan`; sum / mean take the layer's bias and
     ReLU in the kernel epilogue (bias: a tensor that may require grad).  x may be a HalfRows (sum / mean; max without grad)."""
+    table = rows if isinstance(rows, SplitRows) else None
     if isinstance(x, HalfRows):
-        return _aggregate_half(plan, x, op, w_csr, self_coef, bias, act, rows, max_passes)
-    if op == L.MAX:
+        out = _aggregate_half(plan, x, op, w_csr, self_coef, bias, act, rows, max_passes)
+        if out is not None:
+            return out
+        table = x
+        x, w_csr = _half_source(table, w_csr)
+    elif op == L.MAX:
         if self_coef is not None:
             raise NotImplementedError("max aggregation with an implicit self-loop is inference-only")
         h = _AggregateMax.apply(plan, x, w_csr, max_passes)
         if bias is not None:
             h = bias_add(h, bias)
         return torch.relu(h) if act == L.ACT_RELU else h
-    return _Aggregate.apply(plan, op == L.MEAN, x, w_csr, self_coef, rows if isinstance(rows, SplitRows) else None,
-                            bias, act)
+    return _Aggregate.apply(plan, op == L.MEAN, x, w_csr, self_coef, table, bias, act)
 
 
 def _linear_grads(x, kernel, g, need_x, need_k, need_b, gate=None):

@@ -9,7 +9,7 @@ import torch
 
 from ... import _lib as L
 from ...activations import resolve as _resolve_act
-from ...plan import segment_reduce, gemm_bias_act, static_rows, static_aggregate, gather_friendly_empty, aggregate_gemm
+from ...plan import segment_reduce, gemm_bias_act, static_rows, static_aggregate, gather_friendly_empty, aggregate_gemm, HalfRows
 from ...sparse import SparseMatrix, sparse_features, sparse_dense_matmul
 from ... import autograd as AG
 
@@ -32,8 +32,9 @@ class NormedAdj(object):
 
     def matmul(self, h, num_or_size_splits=None, bias=None, act=L.ACT_NONE, cache=None):
         """`cache`: the graph's cache dict — lets repeated products with the SAME h (static input features) switch to
-        the edge-resident-tail layout (plan.static_rows)."""
-        return segment_reduce(self.plan, static_rows(L.as_f32(h), self.plan, cache), L.SUM, w_csr=self.w_csr,
+        the edge-resident-tail layout (plan.static_rows).  h may be a HalfRows (16-bit table), which is read as it is."""
+        rows = h if isinstance(h, HalfRows) else static_rows(L.as_f32(h), self.plan, cache)
+        return segment_reduce(self.plan, rows, L.SUM, w_csr=self.w_csr,
                               self_coef=self.self_coef, bias=bias, act=act)
 
     def __matmul__(self, h):
@@ -162,31 +163,6 @@ def gcn_mapper(repeated_x, neighbor_x, edge_weight=None):
     return _m(repeated_x, neighbor_x, edge_weight)
 
 
-def _gcn_half(h, normed, kernel, bias, activation):
-    """gcn() on a HalfRows (16-bit table) in its aggregation-first form, act((A_hat x) @ kernel + bias) or act(A_hat x + bias):
-    the fused launch on the 16-bit table (tfgx_aggregate_gemm_h16), or tfgx_segment_reduce_h16 followed by the float32 GEMM
-    when it declines.  The static layouts (static_rows / static_aggregate: promotion, memo) are not consulted."""
-    act, post = _resolve_act(activation)
-    plan, w_csr, sc = normed.plan, normed.w_csr, normed.self_coef
-    if AG.needs_grad(h, kernel, bias):
-        bias_t = None if bias is None else L.as_f32(bias)
-        if kernel is None:
-            out = AG.aggregate(plan, h, L.SUM, w_csr, sc, bias=bias_t, act=act)
-        else:
-            out = AG.aggregate_project(plan, h, L.SUM, kernel, w_csr, sc, bias_t, act)
-            if out is None:
-                out = AG.linear(AG.aggregate(plan, h, L.SUM, w_csr, sc), kernel, bias_t, act)
-        return post(out) if post is not None else out
-    bias_t = None if bias is None else L.as_f32(bias).contiguous()
-    if kernel is None:
-        out = segment_reduce(plan, h, L.SUM, w_csr=w_csr, self_coef=sc, bias=bias_t, act=act)
-    else:
-        out = aggregate_gemm(plan, h, L.SUM, kernel, w_csr=w_csr, self_coef=sc, bias=bias_t, act=act)
-        if out is None:
-            out = gemm_bias_act(segment_reduce(plan, h, L.SUM, w_csr=w_csr, self_coef=sc), kernel, bias=bias_t, act=act)
-    return post(out) if post is not None else out
-
-
 def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self_loop=True, sym=True,
         renorm=True, improved=False, edge_drop_rate=0.0, num_or_size_splits=None, training=False, cache=None):
     """
@@ -201,16 +177,15 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     :return: [num_nodes, num_output_features]
     """
     L.require_gpu()
-    from ...plan import HalfRows
-    if isinstance(x, HalfRows):
-        if kernel is not None and not x.F < int(kernel.shape[1]):
-            raise TypeError("gcn multiplies x by its kernel before aggregating when units <= num_features: a HalfRows (16-bit "
-                            "table) is taken by the aggregation kernels only (kernel=None, or units > num_features, where the "
-                            "layer aggregates x itself) — 16-bit GEMM operands are out of scope; pass x.float()")
-        normed = gcn_norm_adj(sparse_adj, norm=norm, add_self_loop=add_self_loop, sym=sym, renorm=renorm,
-                              improved=improved, cache=cache)
-        return _gcn_half(x, normed.dropout(edge_drop_rate, training=training), kernel, bias, activation)
-    xs = sparse_features(x)
+    half = isinstance(x, HalfRows)
+    if half and kernel is not None and not x.F < int(kernel.shape[1]):
+        raise TypeError("gcn multiplies x by its kernel before aggregating when units <= num_features: a HalfRows (16-bit "
+                        "table) is taken by the aggregation kernels only (kernel=None, or units > num_features, where the "
+                        "layer aggregates x itself) — 16-bit GEMM operands are out of scope; pass x.float()")
+    # a 16-bit table takes the aggregation-first branches below on tfgx_aggregate_gemm_h16 / tfgx_segment_reduce_h16 and is read
+    # as it is: the static layouts (plan.static_rows / static_aggregate: promotion, memo) are not consulted
+    layouts = None if half else cache
+    xs = None if half else sparse_features(x)
     if xs is not None:
         # sparse node features (one-hot / bag-of-words rows; tf.sparse.sparse_dense_matmul, :269-270):
         # x @ W is itself a gather-scale-segment-sum with the KERNEL as the source table — the same HIP kernel
@@ -221,16 +196,17 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     normed = gcn_norm_adj(sparse_adj, norm=norm, add_self_loop=add_self_loop, sym=sym, renorm=renorm,
                           improved=improved, cache=cache)                                         # :260
     normed = normed.dropout(edge_drop_rate, training=training)                                    # :262
-    x = L.as_f32(x)
+    x = x if half else L.as_f32(x)
     act, post = _resolve_act(activation)
     if AG.needs_grad(x, kernel, bias):      # training: differentiable un-fused route (autograd.py)
         narrow_first = kernel is not None and int(x.shape[1]) < int(kernel.shape[1])
         h = x if (kernel is None or narrow_first) else AG.linear(x, kernel, gathered=True)
-        rows = static_rows(h, normed.plan, cache) if h is x else None       # raw input features: static across epochs
+        # raw input features: static across epochs
+        rows = static_rows(h, normed.plan, layouts) if (h is x and layouts is not None) else None
         # bias + ReLU ride in the LAST kernel's epilogue (GEMM when the aggregation ran first, else the aggregation)
         bias_t = None if bias is None else L.as_f32(bias)
         if narrow_first:
-            pre = static_aggregate(h, normed.plan, cache, L.SUM, normed.w_csr, normed.self_coef)   # opt-in memo (layer 0)
+            pre = static_aggregate(h, normed.plan, layouts, L.SUM, normed.w_csr, normed.self_coef)   # opt-in memo (layer 0)
             fused = None
             if pre is None:
                 # ONE forward launch (tfgx_aggregate_gemm_f32), on the static feature layout when x has one; the aggregate is
@@ -250,13 +226,13 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     if kernel is not None and int(x.shape[1]) < int(kernel.shape[1]):
         # A_hat @ (x @ W) == (A_hat @ x) @ W: gather at the NARROWER width (bytes per edge = 4*min(F, units) + 8),
         # bias + activation move into the GEMM epilogue. Same result up to fp32 re-association (inside 1e-5).
-        pre = static_aggregate(x, normed.plan, cache, L.SUM, normed.w_csr, normed.self_coef)       # opt-in memo (layer 0)
+        pre = static_aggregate(x, normed.plan, layouts, L.SUM, normed.w_csr, normed.self_coef)     # opt-in memo (layer 0)
         h = None
         if pre is None:
             # one launch: 64-row tiles of A_hat @ x go registers -> LDS -> MFMA against the kernel held in LDS; the
             # [N, F] aggregate never visits HBM (tfgx_aggregate_gemm_f32; None when the shape does not fit).  Source rows: x
             # itself, or its static layout (declared, or promoted on this tensor's second sighting: plan.static_rows)
-            h = aggregate_gemm(normed.plan, static_rows(x, normed.plan, cache), L.SUM, kernel, w_csr=normed.w_csr,
+            h = aggregate_gemm(normed.plan, static_rows(x, normed.plan, layouts), L.SUM, kernel, w_csr=normed.w_csr,
                                self_coef=normed.self_coef, bias=bias_t, act=act)
         if h is None:
             h = gemm_bias_act(pre if pre is not None else normed.matmul(x, cache=cache), kernel, bias=bias_t, act=act)

@@ -27,6 +27,24 @@ def _refuse_half(x, who):
                         "aggregation kernels only — 16-bit GEMM operands are out of scope; pass x.float()".format(who))
 
 
+def _tail(h, post, normalize):
+    """The end of a layer at inference: what the activation leaves to a torch op (post), the in-place l2-normalise kernel."""
+    if post is not None:
+        h = post(h)
+    if normalize:
+        h = l2_normalize_rows_(h.contiguous())
+    return h
+
+
+def _tail_training(h, post, normalize):
+    """The end of a layer with gradients: the l2-normalisation as differentiable torch ops (post=None: already applied)."""
+    if post is not None:
+        h = post(h)
+    if normalize:
+        h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
+    return h
+
+
 def _combine(from_x_kernel, x, from_neigh_kernel, reduced, bias, activation, concat, normalize):
     """concat/add of x @ self_kernel and reduced @ neighbor_kernel, + bias, activation, l2-normalise
     (reference :43-58). With concat the two GEMMs write straight into the two halves of the output."""
@@ -36,15 +54,12 @@ def _combine(from_x_kernel, x, from_neigh_kernel, reduced, bias, activation, con
     if AG.needs_grad(x, reduced, from_x_kernel, from_neigh_kernel, bias):     # training route (autograd.py)
         if concat:      # both GEMMs write into their halves of the output, bias + activation in the epilogues
             h = AG.dual_linear(x, from_x_kernel, reduced, from_neigh_kernel, bias, act)
-            h = post(h) if post is not None else h
         else:
             h = AG.linear(x, from_x_kernel) + AG.linear(reduced, from_neigh_kernel)
             if bias is not None:
                 h = AG.bias_add(h, bias)
             h = AG.apply_activation(h, act, post)
-        if normalize:
-            h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
-        return h
+        return _tail_training(h, post if concat else None, normalize)
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
     if concat:
         h = torch.empty((n, ku_x + ku_n), dtype=torch.float32, device=x.device)
@@ -59,11 +74,7 @@ def _combine(from_x_kernel, x, from_neigh_kernel, reduced, bias, activation, con
             h = h + bias_t
         if act == L.ACT_RELU:
             h = torch.relu_(h)
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = l2_normalize_rows_(h.contiguous())
-    return h
+    return _tail(h, post, normalize)
 
 
 def _neighbor_reduce(x, edge_index, edge_weight, op, cache):
@@ -80,74 +91,41 @@ def _neighbor_reduce(x, edge_index, edge_weight, op, cache):
     return x, segment_reduce(plan, static_rows(x, plan, cache), op, w_csr=w_csr)
 
 
-def _concat_fused(x, edge_index, edge_weight, ws, wn, bias, activation, normalize, op, cache):
-    """Inference, concat, aggregation-first (ku >= F): the neighbour half reduce(w * x[col]) @ W_neigh (+ bias, activation)
-    in ONE launch straight into its half of the output (plan.aggregate_gemm: the [N, F] reduce never visits HBM), the self
-    half by the GEMM.  None when the fused kernel does not take the call (shape / static layouts / hub rows)."""
+def _graph(x, edge_index, edge_weight, cache):
+    """(plan, edge weights in its CSR order) of a layer's square graph."""
     n = int(x.shape[0])
     plan = CsrPlan.from_cache(edge_index, n, n, cache)
-    w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
+    return plan, AG.edge_attr_csr(plan, edge_weight, cache)
+
+
+def _concat_fused(x, plan, w_csr, ws, wn, bias, activation, normalize, op, cache):
+    """Inference, concat, aggregation-first (ku >= F): the neighbour half reduce(w * x[col]) @ W_neigh (+ bias, activation)
+    in ONE launch straight into its half of the output (plan.aggregate_gemm: the [N, F] reduce never visits HBM), the self
+    half by the GEMM.  None when the fused kernel does not take the call (shape / static layouts / hub rows).
+    x: float32, or a HalfRows (tfgx_aggregate_gemm_h16; cache=None: the static layouts are float32-only) whose self half reads
+    the widened table."""
     if static_aggregate_applies(x, cache):
         return None
     act, post = _resolve_act(activation)
-    ku_x, ku_n = int(ws.shape[1]), int(wn.shape[1])
+    n, ku_x, ku_n = int(x.shape[0]), int(ws.shape[1]), int(wn.shape[1])
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
     h = torch.empty((n, ku_x + ku_n), dtype=torch.float32, device=x.device)
     if aggregate_gemm(plan, static_rows(x, plan, cache), op, wn, w_csr=w_csr,
                       bias=None if bias_t is None else bias_t[ku_x:].contiguous(), act=act, out=h[:, ku_x:]) is None:
         return None
-    gemm_bias_act(x, ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = l2_normalize_rows_(h.contiguous())
-    return h
+    # x.float(): a HalfRows widens here (tfgx_rows_h16_to_f32); a float32 tensor is itself
+    gemm_bias_act(x.float(), ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
+    return _tail(h, post, normalize)
 
 
-def _concat_fused_training(x, edge_index, edge_weight, ws, wn, bias, activation, normalize, op, cache):
+def _concat_fused_training(x, plan, w_csr, ws, wn, bias, activation, normalize, op, cache):
     """The same layer body with gradients (autograd.sage_wide): the neighbour half's forward is still one launch; the
     aggregate is written beside it when d/dW_neigh is wanted.  None when the fused kernel does not take the call."""
-    n = int(x.shape[0])
-    plan = CsrPlan.from_cache(edge_index, n, n, cache)
     if static_aggregate_applies(x, cache):
         return None
-    w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
     act, post = _resolve_act(activation)
     h = AG.sage_wide(plan, op, x, ws, wn, w_csr, bias, act, rows=static_rows(x, plan, cache))
-    if h is None:
-        return None
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
-    return h
-
-
-def _concat_fused_half(x, plan, w_csr, ws, wn, bias, activation, normalize, op):
-    """_concat_fused / _concat_fused_training for a HalfRows x: the neighbour half on tfgx_aggregate_gemm_h16, the self half the
-    float32 GEMM on the widened table.  None when the fused launch does not take the call."""
-    act, post = _resolve_act(activation)
-    if AG.needs_grad(x, ws, wn, bias):
-        h = AG.sage_wide(plan, op, x, ws, wn, w_csr, bias, act)
-        if h is None:
-            return None
-        if post is not None:
-            h = post(h)
-        if normalize:
-            h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
-        return h
-    n, ku_x, ku_n = int(x.shape[0]), int(ws.shape[1]), int(wn.shape[1])
-    bias_t = None if bias is None else L.as_f32(bias).contiguous()
-    h = torch.empty((n, ku_x + ku_n), dtype=torch.float32, device=x.device)
-    if aggregate_gemm(plan, x, op, wn, w_csr=w_csr, bias=None if bias_t is None else bias_t[ku_x:].contiguous(), act=act,
-                      out=h[:, ku_x:]) is None:
-        return None
-    gemm_bias_act(x.float(), ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = l2_normalize_rows_(h.contiguous())
-    return h
+    return None if h is None else _tail_training(h, post, normalize)
 
 
 def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel, bias, activation, concat, normalize,
@@ -161,14 +139,13 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
     (tfgx_aggregate_gemm_h16); otherwise the neighbour half aggregates on tfgx_segment_reduce_h16 into float32 and the
     projections run on the float32 GEMM.  The self half reads x.float()."""
     if isinstance(x, HalfRows):
-        n = int(x.shape[0])
-        plan = CsrPlan.from_cache(edge_index, n, n, cache)
-        w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
+        plan, w_csr = _graph(x, edge_index, edge_weight, cache)
         ws, wn = L.as_f32(self_kernel), L.as_f32(neighbor_kernel)
         if not int(wn.shape[1]) < x.F and concat and not AG.needs_grad(edge_weight):
             # aggregation first, concat: the neighbour half is ONE launch on the 16-bit table (tfgx_aggregate_gemm_h16) straight
             # into its half of the output — inference and training as on the float32 path; None: the launch declines
-            h = _concat_fused_half(x, plan, w_csr, ws, wn, bias, activation, normalize, op)
+            fused = _concat_fused_training if AG.needs_grad(x, ws, wn, bias) else _concat_fused
+            h = fused(x, plan, w_csr, ws, wn, bias, activation, normalize, op, None)
             if h is not None:
                 return h
         reduced = AG.aggregate(plan, x, op, w_csr) if AG.needs_grad(x, edge_weight) else segment_reduce(plan, x, op, w_csr=w_csr)
@@ -179,40 +156,36 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
     F, ku_x, ku_n = int(x.shape[1]), int(ws.shape[1]), int(wn.shape[1])
     if not ku_n < F:
         if concat and not AG.needs_grad(x, edge_weight, ws, wn, bias):
-            h = _concat_fused(x, edge_index, edge_weight, ws, wn, bias, activation, normalize, op, cache)
+            h = _concat_fused(x, *_graph(x, edge_index, edge_weight, cache), ws, wn, bias, activation, normalize, op, cache)
             if h is not None:
                 return h
         if concat and not AG.needs_grad(edge_weight):
-            h = _concat_fused_training(x, edge_index, edge_weight, ws, wn, bias, activation, normalize, op, cache)
+            h = _concat_fused_training(x, *_graph(x, edge_index, edge_weight, cache), ws, wn, bias, activation, normalize, op,
+                                       cache)
             if h is not None:
                 return h
         x, reduced = _neighbor_reduce(x, edge_index, edge_weight, op, cache)
         return _combine(ws, x, wn, reduced, bias, activation, concat, normalize)
     n = int(x.shape[0])
-    plan = CsrPlan.from_cache(edge_index, n, n, cache)
-    w_csr = AG.edge_attr_csr(plan, edge_weight, cache)
+    plan, w_csr = _graph(x, edge_index, edge_weight, cache)
     act, post = _resolve_act(activation)
     if AG.needs_grad(x, edge_weight, ws, wn, bias):
         if concat and not AG.needs_grad(w_csr):
             # one fused operator: both halves written in place, bias + activation in the GEMM's / the aggregation's
             # epilogue — no concat, no bias add, no activation pass
             h = AG.sage_narrow(plan, op, x, ws, wn, w_csr, bias, act)
-            h = post(h) if post is not None else h
         elif concat:    # trainable edge weights: the un-fused operators carry d/dw
             bias_t = None if bias is None else L.as_f32(bias)
             a = AG.linear(x, ws, None if bias_t is None else bias_t[:ku_x], act)
             b = AG.aggregate(plan, AG.linear(x, wn, gathered=True), op, w_csr,
                              bias=None if bias_t is None else bias_t[ku_x:], act=act)
             h = torch.cat([a, b], dim=1)
-            h = post(h) if post is not None else h
         else:
             h = AG.linear(x, ws) + AG.aggregate(plan, AG.linear(x, wn, gathered=True), op, w_csr)
             if bias is not None:
                 h = AG.bias_add(h, bias)
             h = AG.apply_activation(h, act, post)
-        if normalize:
-            h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
-        return h
+        return _tail_training(h, post if concat else None, normalize)
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
     z = gemm_bias_act(x, wn, out=gather_friendly_empty(n, ku_n, x.device))      # rows gathered next: line-friendly stride
     if concat:
@@ -222,11 +195,7 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
                        bias=None if bias_t is None else bias_t[ku_x:].contiguous())
     else:
         h = segment_reduce(plan, z, op, w_csr=w_csr, add_x=gemm_bias_act(x, ws), bias=bias_t, act=act)
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = l2_normalize_rows_(h.contiguous())
-    return h
+    return _tail(h, post, normalize)
 
 
 def mean_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel, bias=None, activation=None,
@@ -278,13 +247,10 @@ def gcn_graph_sage(x, edge_index, edge_weight, kernel, bias=None, activation=Non
         if narrow:
             h = AG.aggregate(normed.plan, AG.linear(x, kernel, gathered=True), L.SUM, normed.w_csr, normed.self_coef,
                              bias=None if bias is None else L.as_f32(bias), act=act)
-            h = post(h) if post is not None else h
         else:
             reduced = AG.aggregate(normed.plan, x, L.SUM, normed.w_csr, normed.self_coef)
             h = AG.apply_activation(AG.linear(reduced, kernel, bias, act), L.ACT_NONE, post)
-        if normalize:
-            h = h * torch.rsqrt(torch.clamp((h * h).sum(-1, keepdim=True), min=1e-12))
-        return h
+        return _tail_training(h, post if narrow else None, normalize)
     if narrow:
         z = gemm_bias_act(x, kernel, out=gather_friendly_empty(n, int(kernel.shape[1]), x.device))
         h = normed.matmul(z, bias=None if bias is None else L.as_f32(bias).contiguous(), act=act)
@@ -293,11 +259,7 @@ def gcn_graph_sage(x, edge_index, edge_weight, kernel, bias=None, activation=Non
         if h is None:
             reduced = normed.matmul(x)                                              # :143-150
             h = gemm_bias_act(reduced, kernel, bias=bias, act=act)                  # :152-157
-    if post is not None:
-        h = post(h)
-    if normalize:
-        h = l2_normalize_rows_(h)
-    return h
+    return _tail(h, post, normalize)
 
 
 def _pool_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_mlp_kernel, neighbor_kernel,
@@ -343,11 +305,7 @@ def _pool_graph_sage(x, edge_index, edge_weight, self_kernel, neighbor_mlp_kerne
                            bias=None if bias_t is None else bias_t[ku_x:].contiguous())
         else:
             out = segment_reduce(plan, z, L.MEAN, add_x=gemm_bias_act(x, ws), bias=bias_t, act=act)
-        if post is not None:
-            out = post(out)
-        if normalize:
-            out = l2_normalize_rows_(out.contiguous())
-        return out
+        return _tail(out, post, normalize)
     reduced = segment_reduce(plan, h, op)                                            # :206 / :269
     return _combine(ws, x, wn, reduced, bias, activation, concat, normalize)
 
