@@ -587,6 +587,36 @@ def test_fused_aggregate_gemm_on_a_graph_with_hub_rows(tfg, oracle, mode, f, uni
     assert_parity(fused.cpu().numpy(), two.cpu().numpy(), what="fused with hub rows vs two launches")
 
 
+@pytest.mark.parametrize("units", [256, 254])
+def test_fused_aggregate_gemm_walk_order_with_a_streamed_kernel(tfg, oracle, units):
+    """The float32 launch walking its rows in degree order while half of the kernel's columns are read from global memory:
+    F = 128 keeps 128 of 256 columns in LDS, n = 130 is two full tiles and a 2-row tail, units = 256 stores 16 bytes per
+    lane through the row ids in LDS and 254 takes the per-column stores.  The smallest shape with this combination; the
+    rows equal the two launches' bit for bit."""
+    import torch
+    from tf_geometric_amd import plan as P
+    L = tfg._lib
+    n, f = 130, 128
+    rng = np.random.Generator(np.random.PCG64(units))
+    ei = oracle.synthetic_edges(n, 700, seed=units)
+    long_row = np.stack([np.full(100, 77, np.int32), rng.integers(0, n, size=100, dtype=np.int32)])     # skewed (a walk order), no hub row
+    ei = np.concatenate([ei, long_row], axis=1)
+    plan = P.CsrPlan.build(L.as_i32(ei), n, n)
+    order = plan.row_order()
+    assert order is not None and int(order[0]) == 77 and plan.hub_info() is None
+    xd = L.as_f32(rng.standard_normal((n, f), dtype=np.float32))
+    kd = L.as_f32(oracle.glorot_uniform(rng, f, units))
+    bd = L.as_f32((rng.standard_normal(units) * 0.1).astype(np.float32))
+    w_csr = plan.edge_attr_to_csr(rng.uniform(0.5, 1.5, ei.shape[1]).astype(np.float32))
+    sc = L.as_f32(rng.uniform(0.25, 1.25, n).astype(np.float32))
+    before = P.FUSED_STATS["launches"]
+    fused = P.aggregate_gemm(plan, xd, L.SUM, kd, w_csr=w_csr, self_coef=sc, bias=bd, act=L.ACT_RELU)
+    assert fused is not None and P.FUSED_STATS["launches"] == before + 1
+    two = P.gemm_bias_act(P.segment_reduce(plan, xd, L.SUM, w_csr=w_csr, self_coef=sc), kd, bias=bd, act=L.ACT_RELU)
+    assert torch.equal(fused, two), "{} elements differ, max |d| = {:.3e}".format(
+        int((fused != two).sum()), float((fused - two).abs().max()))
+
+
 @pytest.mark.parametrize("m,k,n", [(300001, 100, 256), (280000, 256, 256), (262144, 128, 96), (270000, 36, 40)])
 def test_gemm_dynamic_tile_order_changes_no_bit(tfg, oracle, m, k, n):
     """Tall products (M >= 2^18) given a workspace run the row kernel with CLAIMED tiles (per-pool device counters in the

@@ -29,8 +29,10 @@ def build(force=False, verbose=True):
     h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_h16.h")
     fused_h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_fused_h16.h")
     # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
+    fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
-                "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr, os.path.join(CSRC, "tfgx_mfma.h")],
+                "tfgx_fused.hip": fused_hdrs,
+                "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr] + fused_hdrs,
                 "tfgx_dropedge.hip": [os.path.join(_HERE, "..", "include", "tfgx_dropedge.h")],
                 "tfgx_linkpred.hip": [os.path.join(_HERE, "..", "include", "tfgx_linkpred.h")],
                 "tfgx_lstm.hip": [os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],

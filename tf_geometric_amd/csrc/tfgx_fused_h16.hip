@@ -16,10 +16,9 @@
 // store nothing), wider rows G = 16.  The alternative — a job count that follows G — would leave a tile of narrow rows to
 // four or fewer consumer waves, the situation JB = 2 / eight jobs was introduced against in the fp32 kernel.
 //
-// The consumer below is a copy of tfgx_fused.hip's (that file's code generation must not move), less its developer
-// switches; k order, accumulator layout and epilogue are the same expressions.
-#include "tfgx_common.h"
-#include "tfgx_mfma.h"
+// The LDS set-up, the consumer (hand-over, MFMA loops, epilogue, stores) and the host side of the launch are shared with
+// tfgx_fused.hip: tfgx_fused_common.h.
+#include "tfgx_fused_common.h"
 #include "../../include/tfgx_fused_h16.h"
 #include <cstdio>
 #include <cstring>
@@ -28,38 +27,17 @@
 namespace tfgx {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTileRows = 64;
-constexpr int kLda = kTileRows + 1;
-constexpr int kBufs = 2;
-constexpr int kFusedThreads = 1024;
 constexpr int kVec = 8;      // elements per 16-byte vector of a 16-bit table
-constexpr int kJB = 2;       // 32-column blocks per consumer job
 
-struct FHArgs {
+struct FHArgs : FusedProj {
     const int32_t* row_ptr;
     const int32_t* col;
     const float* w;
-    int64_t n_dst;
     const uint16_t* x;      // [n_src, ldx] 16-bit elements
     int64_t ldx;
-    int32_t F;
     int32_t op;
     const float* self_coef;
     const int32_t* mean_count;
-    const float* B;
-    int64_t ldb;
-    const float* bias;
-    int32_t act;
-    int32_t N;
-    float* C;
-    int64_t ldc;
-    int32_t KP;        // F rounded up to even (the MFMA consumes two k per step)
-    int32_t n_blocks;  // 32-column output blocks, rounded up to a multiple of 4
-    int32_t LDW;       // NL + 8
-    int64_t n_tiles;
-    int32_t NL;        // columns of B resident in LDS (multiple of 64); columns >= NL: B operand from global
     float* agg;        // optional side output: the aggregated rows themselves, [n_dst, ld_agg] fp32, or NULL
     int64_t ld_agg;
     int32_t hub_threshold;
@@ -67,14 +45,8 @@ struct FHArgs {
     const int32_t* hub_rows;        // ascending
     const int32_t* hub_chunk_ptr;
     const float* hub_scratch;       // [chunks, F] fp32 chunk partials (written by tfgx_segment_reduce_h16 before this launch)
-    const int32_t* row_order;
     const int32_t* hub_order_slot;
 };
-
-template <int G>
-__device__ __forceinline__ int bcast_i(int v, int j) { return __shfl(v, j, G); }
-template <int G>
-__device__ __forceinline__ float bcast_f(float v, int j) { return __shfl(v, j, G); }
 
 // 16-bit -> fp32 in registers (exact): the expressions of tfgx_reduce_h16.hip
 template <int DT>
@@ -97,24 +69,13 @@ template <int DT, int G, bool WEIGHTED>
 __global__ __launch_bounds__(kFusedThreads) void agg_gemm_h16_kernel(const FHArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* Ws = lds;                                        // [KP][LDW]
-    float* At = Ws + a.KP * a.LDW;                          // [kBufs][KP][kLda]
-    int* ctrl = reinterpret_cast<int*>(At + kBufs * a.KP * kLda);   // [0] next unit | [1 + b] arrivals of buffer b | [1 + kBufs + b] done seq
-    int* rowid = ctrl + 16;                                 // [kBufs][kTileRows]: the destination row of each tile slot (row_order)
+    const FusedLds sh = fused_lds_init(a, lds);
     constexpr int RPW = 64 / G;                             // destination rows per wave step (one per lane group)
     constexpr int UNITS = kTileRows / RPW;
     constexpr int UNROLL = 8;
     static_assert(G == 8 || G == 16, "UNITS = G must cover the eight consumer jobs of a tile");
     const int tid = threadIdx.x, lane64 = tid & 63;
     const int lane = lane64 % G, grp = lane64 / G;
-
-    for (int i = tid; i < a.KP * a.LDW; i += kFusedThreads) {
-        const int k = i / a.LDW, n = i - k * a.LDW;
-        Ws[i] = (k < a.F && n < a.N && n < a.NL) ? a.B[int64_t(k) * a.ldb + n] : 0.0f;
-    }
-    for (int i = tid; i < kBufs * a.KP * kLda; i += kFusedThreads) At[i] = 0.0f;      // rows k >= F stay zero for good
-    if (tid < 16) ctrl[tid] = 0;                            // ([6 + b]: finished jobs of buffer b's tile)
-    __syncthreads();
 
     const int64_t my_tiles = a.n_tiles > int64_t(blockIdx.x) ? (a.n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
     const int64_t total_units = my_tiles * UNITS;
@@ -126,8 +87,6 @@ __global__ __launch_bounds__(kFusedThreads) void agg_gemm_h16_kernel(const FHArg
     const int coff = (v_lo || int64_t(c0) + kVec <= a.ldx) ? c0 : 0;
     // fp32 rows of F columns (hub partials): a half past F re-reads the last valid vector (discarded)
     const int h_lo = v_lo ? c0 : a.F - 4, h_hi = v_hi ? c0 + 4 : a.F - 4;
-    const int l31 = lane64 & 31, kh = lane64 >> 5;
-    const bool vec_store = (a.N % 4 == 0) && (a.ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.C) & 15) == 0);      // wave-uniform
     const uint16_t* xb = a.x + coff;
     // element offset of a gathered row as ONE 32 x 32 -> 64-bit multiply: ids are non-negative int32, the stride fits 32 bits
     const uint32_t xl32 = uint32_t(a.ldx);
@@ -135,7 +94,7 @@ __global__ __launch_bounds__(kFusedThreads) void agg_gemm_h16_kernel(const FHArg
 
     while (true) {
         int u = 0;
-        if (lane64 == 0) u = atomicAdd(&ctrl[0], 1);
+        if (lane64 == 0) u = atomicAdd(&sh.ctrl[0], 1);
         u = __builtin_amdgcn_readfirstlane(u);
         if (u >= total_units) break;
         const int q = u / UNITS, slot = u - q * UNITS;      // tile sequence number inside this workgroup, unit inside the tile
@@ -257,13 +216,9 @@ __global__ __launch_bounds__(kFusedThreads) void agg_gemm_h16_kernel(const FHArg
             if (v_lo) store_vec<4>(a.agg + r * a.ld_agg + c0, lo4);
             if (v_hi) store_vec<4>(a.agg + r * a.ld_agg + c0 + 4, hi4);
         }
-        // ---- hand the row over: wait until the buffer's previous tile (q - kBufs) has been multiplied, store transposed
-        if (q >= kBufs) {
-            volatile int* done = ctrl + 1 + kBufs + buf;
-            while (*done < q - kBufs + 1) __builtin_amdgcn_s_sleep(1);
-            __threadfence_block();
-        }
-        float* ab = At + buf * a.KP * kLda;
+        // ---- hand the row over: wait until the buffer's previous tile has been multiplied, store transposed ----------------
+        fused_wait_buffer(sh, q, buf);
+        float* ab = sh.At + buf * a.KP * kLda;
         if (v_lo) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) ab[(c0 + v) * kLda + m] = acc[v];
@@ -272,198 +227,9 @@ __global__ __launch_bounds__(kFusedThreads) void agg_gemm_h16_kernel(const FHArg
 #pragma unroll
             for (int v = 4; v < kVec; ++v) ab[(c0 + v) * kLda + m] = acc[v];
         }
-        if (a.row_order != nullptr && lane == 0) rowid[buf * kTileRows + m] = ri < a.n_dst ? int(r) : -1;
-        __threadfence_block();
-        int arrived = 0;
-        if (lane64 == 0) arrived = atomicAdd(&ctrl[1 + buf], 1);
-        arrived = __builtin_amdgcn_readfirstlane(arrived);
-        constexpr int JB = kJB;
-        const int njobs = 2 * (a.n_blocks / JB);             // 4 (N <= 128) or 8: never more than UNITS = G >= 8
-        if (arrived < UNITS - njobs) continue;
-
-        // ---- consumers: the last arrivers of tile q each multiply ONE 32-row x (32 JB)-column block of it (the last one at
-        // once, the ones before it as soon as the tile is complete) -> C[tile rows, :] = act(At^T @ Ws + bias)
-        const int job = UNITS - 1 - arrived;                 // the last arriver takes block 0, the one before it block 1, ...
-        if (job > 0) {
-            volatile int* arr = ctrl + 1 + buf;
-            while (*arr < UNITS) __builtin_amdgcn_s_sleep(1);
-        }
-        __threadfence_block();
-        const int mb = job & 1, nb0 = (job >> 1) * JB;
-        {
-            f32x16 c4[JB];
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-                for (int t = 0; t < 16; ++t) c4[jb][t] = 0.0f;
-            const float* ap = ab + kh * kLda + mb * 32 + l31;
-            const int pairs = a.KP / 2;
-            int pr = 0;
-            if (nb0 * 32 < a.NL) {
-                // B resident in LDS.  KU k-pairs per step: all (1 + JB) * KU LDS reads of a step are issued before its
-                // JB * KU MFMAs
-                const float* bp = Ws + kh * a.LDW + nb0 * 32 + l31;
-                constexpr int KU = 4;
-                for (; pr + KU <= pairs; pr += KU) {
-                    float av[KU], bv[KU][JB];
-#pragma unroll
-                    for (int t = 0; t < KU; ++t) {
-                        av[t] = ap[(2 * (pr + t)) * kLda];
-#pragma unroll
-                        for (int jb = 0; jb < JB; ++jb) bv[t][jb] = bp[(2 * (pr + t)) * a.LDW + jb * 32];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);      // left alone the scheduler sinks every read next to its MFMA
-#pragma unroll
-                    for (int t = 0; t < KU; ++t)
-#pragma unroll
-                        for (int jb = 0; jb < JB; ++jb)
-                            c4[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t][jb], c4[jb], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                for (; pr < pairs; ++pr) {
-                    const float av = ap[(2 * pr) * kLda];
-                    float bv[JB];
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb) bv[jb] = bp[(2 * pr) * a.LDW + jb * 32];
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb) c4[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[jb], c4[jb], 0, 0, 0);
-                }
-            } else {
-                // B columns past the resident ones: the operand comes from global memory (L2: every workgroup re-reads the
-                // same <= 128 KB for every tile).  Lane (l31, kh) reads B[2 pr + kh][col]; KG k-pairs = JB * KG loads in
-                // flight per wave before the first MFMA of the step.  Columns >= N read column N - 1 (never stored).
-                const float* gp[JB];
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    const int gn = (nb0 + jb) * 32 + l31;
-                    gp[jb] = a.B + int64_t(kh) * a.ldb + (gn < a.N ? gn : a.N - 1);
-                }
-                constexpr int KG = 8;
-                for (; pr + KG <= pairs; pr += KG) {
-                    float av[KG], bv[KG][JB];
-#pragma unroll
-                    for (int t = 0; t < KG; ++t)
-#pragma unroll
-                        for (int jb = 0; jb < JB; ++jb) bv[t][jb] = gp[jb][int64_t(2 * (pr + t)) * a.ldb];
-#pragma unroll
-                    for (int t = 0; t < KG; ++t) av[t] = ap[(2 * (pr + t)) * kLda];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int t = 0; t < KG; ++t)
-#pragma unroll
-                        for (int jb = 0; jb < JB; ++jb)
-                            c4[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t][jb], c4[jb], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                for (; pr < pairs; ++pr) {
-                    const float av = ap[(2 * pr) * kLda];
-                    float bv[JB];
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb) bv[jb] = (2 * pr + kh < a.F) ? gp[jb][int64_t(2 * pr) * a.ldb] : 0.0f;
-#pragma unroll
-                    for (int jb = 0; jb < JB; ++jb) c4[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[jb], c4[jb], 0, 0, 0);
-                }
-            }
-            // D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).  Two phases on purpose: bias +
-            // activation IN PLACE first, then every store reads its own accumulator register
-#pragma unroll
-            for (int jb = 0; jb < JB; ++jb) {
-                const int gn = (nb0 + jb) * 32 + l31;
-                const float bv = (a.bias && gn < a.N) ? a.bias[gn] : 0.0f;
-#pragma unroll
-                for (int t = 0; t < 16; ++t) c4[jb][t] = apply_act(c4[jb][t] + bv, a.act);
-            }
-            const int64_t row0 = tile * kTileRows + mb * 32 + 4 * kh;
-            const bool full = tile * kTileRows + kTileRows <= a.n_dst;
-            if (a.row_order != nullptr && !vec_store) {     // walk order without 16-byte stores (odd N / unaligned C)
-                const int* rid = rowid + buf * kTileRows + mb * 32 + 4 * kh;
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    const int gn = (nb0 + jb) * 32 + l31;
-                    if (gn >= a.N) continue;
-#pragma unroll
-                    for (int t = 0; t < 16; ++t) {
-                        const int rr = rid[(t & 3) + 8 * (t >> 2)];
-                        if (rr >= 0) __builtin_nontemporal_store(c4[jb][t], a.C + int64_t(rr) * a.ldc + gn);
-                    }
-                }
-            } else if (vec_store && (full || a.row_order != nullptr)) {
-                // 16-byte stores through a quad transpose of the accumulators (tfgx_mfma.h): lane i of a quad ends with row
-                // 8 g + i + 4 kh, columns 4 q .. 4 q + 3
-                const int qi = lane64 & 3, qc = (l31 >> 2) * 4;
-                typedef float f32x4s __attribute__((ext_vector_type(4)));
-                int64_t roff[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int sl = mb * 32 + 8 * g + qi + 4 * kh;
-                    const int64_t rr = a.row_order != nullptr ? int64_t(rowid[buf * kTileRows + sl]) : tile * kTileRows + sl;
-                    roff[g] = rr >= 0 ? rr * a.ldc : int64_t(-1);
-                }
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    float r4[4][4];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {          // (every lane takes part in the quad permutes)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) r4[g][k] = c4[jb][4 * g + k];
-                        quad_transpose4(r4[g], lane64);
-                    }
-                    const int gn = (nb0 + jb) * 32 + qc;
-                    if (gn < a.N) {
-#pragma unroll
-                        for (int g = 0; g < 4; ++g)
-                            if (roff[g] >= 0)
-                                __builtin_nontemporal_store(f32x4s{r4[g][0], r4[g][1], r4[g][2], r4[g][3]},
-                                                            reinterpret_cast<f32x4s*>(a.C + roff[g] + gn));
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int jb = 0; jb < JB; ++jb) {
-                    const int gn = (nb0 + jb) * 32 + l31;
-                    if (gn >= a.N) continue;
-                    float* cp = a.C + row0 * a.ldc + gn;
-                    if (full) {
-#pragma unroll
-                        for (int t = 0; t < 16; ++t)
-                            __builtin_nontemporal_store(c4[jb][t], cp + int64_t((t & 3) + 8 * (t >> 2)) * a.ldc);
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 16; ++t) {
-                            const int dr = (t & 3) + 8 * (t >> 2);
-                            if (row0 + dr < a.n_dst) cp[int64_t(dr) * a.ldc] = c4[jb][t];
-                        }
-                    }
-                }
-            }
-        }
-        __threadfence_block();
-        int fin = 0;
-        if (lane64 == 0) fin = atomicAdd(&ctrl[6 + buf], 1);
-        fin = __builtin_amdgcn_readfirstlane(fin);
-        if (fin == njobs - 1) {
-            // the last job to finish hands the buffer back (wave-uniform branch; every lane stores the same values)
-            ctrl[1 + buf] = 0;
-            ctrl[6 + buf] = 0;
-            __threadfence_block();
-            *reinterpret_cast<volatile int*>(ctrl + 1 + kBufs + buf) = q + 1;
-        }
+        if (a.row_order != nullptr && lane == 0) sh.rowid[buf * kTileRows + m] = ri < a.n_dst ? int(r) : -1;
+        fused_arrive_and_multiply<UNITS>(a, sh, q, buf, tile, lane64);
     }
-}
-
-// LDS budget: the arithmetic of tfgx_fused.hip (the envelope itself is tfgx_aggregate_gemm_fits, not restated here)
-inline size_t fused_lds_bytes(int kp, int ldw)
-{
-    return sizeof(float) * (size_t(kp) * ldw + size_t(kBufs) * kp * kLda) + sizeof(int) * (16 + kBufs * kTileRows);
-}
-
-constexpr size_t kFusedLdsLimit = 160 * 1024;
-
-inline int fused_resident_cols(int kp, int np)
-{
-    for (int nl = np; nl >= 64; nl -= 64)
-        if (fused_lds_bytes(kp, nl + 8) <= kFusedLdsLimit) return nl;
-    return 0;
 }
 
 inline int group_lanes(int64_t F) { return F <= 64 ? 8 : 16; }      // the ONE place G is decided (launch and describe)
@@ -506,26 +272,14 @@ int check_fused_h16(const char* fn, const tfgx_reduce_args* p, int32_t x_dtype, 
     return TFGX_OK;
 }
 
-template <int DT, int G, bool WEIGHTED>
-int launch_one(const FHArgs& a, int dev, int64_t wgs, size_t lds_bytes, hipStream_t stream)
-{
-    constexpr int kMaxDev = 64;
-    static bool attr_set[kMaxDev] = {false};      // per DEVICE and instantiation: the dynamic-LDS attribute
-    if (!attr_set[dev]) {
-        TFGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(agg_gemm_h16_kernel<DT, G, WEIGHTED>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(kFusedLdsLimit)));
-        attr_set[dev] = true;
-    }
-    agg_gemm_h16_kernel<DT, G, WEIGHTED><<<dim3(unsigned(wgs)), dim3(kFusedThreads), lds_bytes, stream>>>(a);
-    TFGX_LAUNCH_CHECK("agg_gemm_h16_kernel");
-    return TFGX_OK;
-}
-
 template <int DT>
-int launch_dt(const FHArgs& a, int g, bool weighted, int dev, int64_t wgs, size_t lds_bytes, hipStream_t stream)
+int launch_dt(const char* fn, const FHArgs& a, int g, bool weighted, hipStream_t stream)
 {
-    if (g == 8) return weighted ? launch_one<DT, 8, true>(a, dev, wgs, lds_bytes, stream) : launch_one<DT, 8, false>(a, dev, wgs, lds_bytes, stream);
-    return weighted ? launch_one<DT, 16, true>(a, dev, wgs, lds_bytes, stream) : launch_one<DT, 16, false>(a, dev, wgs, lds_bytes, stream);
+    const char* name = "agg_gemm_h16_kernel";
+    if (g == 8) return weighted ? fused_launch<agg_gemm_h16_kernel<DT, 8, true>>(fn, name, a, stream)
+                                : fused_launch<agg_gemm_h16_kernel<DT, 8, false>>(fn, name, a, stream);
+    return weighted ? fused_launch<agg_gemm_h16_kernel<DT, 16, true>>(fn, name, a, stream)
+                    : fused_launch<agg_gemm_h16_kernel<DT, 16, false>>(fn, name, a, stream);
 }
 
 }  // namespace
@@ -563,15 +317,7 @@ extern "C" int tfgx_aggregate_gemm_h16(const tfgx_reduce_args* p, int32_t x_dtyp
     if (use_hub) {
         // chunk partials first: every chunk is reduced like an ordinary row of the 16-bit table into the fp32 hub_scratch
         // (tfgx_segment_reduce_h16 — the bits tfgx_segment_reduce_f32 leaves there for the widened table)
-        tfgx_reduce_args c = *p;
-        c.row_begin = p->hub_chunk_begin; c.row_end = p->hub_chunk_end; c.rp_stride = 1;
-        c.n_dst = p->n_hub_chunks; c.out = p->hub_scratch; c.ldo = p->F;
-        c.op = TFGX_SUM; c.act = TFGX_ACT_NONE; c.accumulate = 0;
-        c.self_coef = nullptr; c.bias = nullptr; c.add_x = nullptr; c.mean_count = nullptr;
-        c.hub_threshold = 0; c.hub_rows = nullptr; c.hub_chunk_ptr = nullptr; c.hub_chunk_begin = nullptr;
-        c.hub_chunk_end = nullptr; c.n_hub_rows = 0; c.n_hub_chunks = 0; c.hub_scratch = nullptr;
-        c.row_order = nullptr;          // (a walk order names DESTINATION rows; the chunk launch walks chunks)
-        c.hub_order_slot = nullptr;
+        const tfgx_reduce_args c = fused_hub_chunk_args(p);
         const int rc = tfgx_segment_reduce_h16(&c, x_dtype, TFGX_DT_F32, stream_);
         if (rc != TFGX_OK) return rc;
     }
@@ -579,34 +325,15 @@ extern "C" int tfgx_aggregate_gemm_h16(const tfgx_reduce_args* p, int32_t x_dtyp
     a.hub_threshold = use_hub ? p->hub_threshold : 0;
     a.n_hub = use_hub ? int32_t(p->n_hub_rows) : 0;
     a.hub_rows = p->hub_rows; a.hub_chunk_ptr = p->hub_chunk_ptr; a.hub_scratch = p->hub_scratch;
-    a.row_order = p->row_order;
     a.hub_order_slot = use_hub ? p->hub_order_slot : nullptr;
-    a.row_ptr = p->row_begin; a.col = p->col; a.w = p->w; a.n_dst = p->n_dst;
-    a.x = static_cast<const uint16_t*>(static_cast<const void*>(p->x)); a.ldx = p->ldx; a.F = int32_t(p->F);
+    a.row_ptr = p->row_begin; a.col = p->col; a.w = p->w;
+    a.x = static_cast<const uint16_t*>(static_cast<const void*>(p->x)); a.ldx = p->ldx;
     a.op = p->op; a.self_coef = p->self_coef; a.mean_count = p->mean_count;
-    a.B = B; a.ldb = ldb; a.bias = bias; a.act = act; a.N = int32_t(N); a.C = C; a.ldc = ldc;
+    fused_fill_proj(a, p, B, ldb, bias, act, C, ldc, N);
     a.agg = static_cast<float*>(p->out); a.ld_agg = p->ldo;
-    a.KP = int32_t((p->F + 1) / 2 * 2);
-    a.n_blocks = int32_t((N + 127) / 128) * 4;          // 32-column blocks, in groups of four (columns >= N are zero in LDS)
-    a.NL = fused_resident_cols(a.KP, 32 * a.n_blocks);
-    a.LDW = a.NL + 8;
-    a.n_tiles = (p->n_dst + kTileRows - 1) / kTileRows;
-    constexpr int kMaxDev = 64;
-    static int cus_of[kMaxDev] = {0};
-    int dev = 0;
-    TFGX_HIP_CHECK(hipGetDevice(&dev));
-    TFGX_REQUIRE(dev >= 0 && dev < kMaxDev, "device ordinal out of range");
-    if (cus_of[dev] == 0) {
-        hipDeviceProp_t prop;
-        TFGX_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        cus_of[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int cus = cus_of[dev];
-    const size_t lds_bytes = fused_lds_bytes(a.KP, a.LDW);
-    const int64_t wgs = a.n_tiles < cus ? a.n_tiles : cus;
     hipStream_t stream = as_stream(stream_);
     const bool weighted = p->w != nullptr;
     const int g = group_lanes(p->F);
-    if (x_dtype == TFGX_DT_BF16) return launch_dt<TFGX_DT_BF16>(a, g, weighted, dev, wgs, lds_bytes, stream);
-    return launch_dt<TFGX_DT_F16>(a, g, weighted, dev, wgs, lds_bytes, stream);
+    if (x_dtype == TFGX_DT_BF16) return launch_dt<TFGX_DT_BF16>(__func__, a, g, weighted, stream);
+    return launch_dt<TFGX_DT_F16>(__func__, a, g, weighted, stream);
 }

@@ -1,4 +1,4 @@
-// Small helpers shared by the MFMA kernels (tfgx_gemm.hip, tfgx_fused.hip).
+// Small helpers shared by the MFMA kernels (tfgx_gemm.hip, tfgx_fused_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
