@@ -346,6 +346,20 @@ ASAP_SIGNATURES = {
     "tfgx_spasp_reduce": (ctypes.c_int, [_I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# include/tfgx_seggram.h (the segmented transposed product S_g^T Y_g of DiffPool / MinCutPool and its backward): its own
+# header, version and table — checked against that header by tests/test_seggram_abi.py.
+SEGGRAM_ABI_VERSION = 1
+SEGGRAM_MAX_K = 64
+SEGGRAM_BLOCK = 64
+SEGGRAM_SIGNATURES = {
+    "tfgx_seggram_version": (ctypes.c_int, []),
+    "tfgx_seggram_block": (ctypes.c_int, []),
+    "tfgx_segment_gram_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "tfgx_segment_gram_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "tfgx_segment_gram_backward_f32": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P,
+                                                      _I64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -397,6 +411,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in SEGGRAM_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_seggram_version() != SEGGRAM_ABI_VERSION or lib.tfgx_seggram_block() != SEGGRAM_BLOCK:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_seggram ABI {} (block {}) but this package binds {} (block {}) "
+                        "(include/tfgx_seggram.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_seggram_version(), lib.tfgx_seggram_block(), SEGGRAM_ABI_VERSION, SEGGRAM_BLOCK))
     if lib.tfgx_asap_version() != ASAP_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_asap ABI {} but this package binds {} "
                         "(include/tfgx_asap.h): rebuild with __graft_entry__.build()".format(

@@ -1539,3 +1539,69 @@ def asap_attend(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
                                                     bias.detach().contiguous(), drop_rate, seed)
         return (c, p, p_self) if pd is None else (c, pd, pds)
     return asap_attend_composed(plan, x, sq, sh, bias, drop_rate, seed)
+
+
+def segment_gram_forward(graph_plan, S, Y, bad_flag=None):
+    """One tfgx_segment_gram_f32 call on a graph plan (rows = graphs, col = node ids): out [G * K, W] with
+    out[g K + k, w] = sum over the nodes n of graph g, in the plan's order, of S[n, k] Y[n, w]."""
+    lib = L.require_gpu()
+    S, lds = L.row_major_2d(S)
+    Y, ldy = L.row_major_2d(Y)
+    G, N, K, W = graph_plan.n_dst, int(S.shape[0]), int(S.shape[1]), int(Y.shape[1])
+    if int(Y.shape[0]) != N or graph_plan.num_edges != N:
+        raise ValueError("segment_gram: S has {} rows, Y {} and the graph plan names {} nodes".format(
+            N, int(Y.shape[0]), graph_plan.num_edges))
+    if not 1 <= K <= L.SEGGRAM_MAX_K:
+        raise ValueError("segment_gram: {} clusters per graph, TFGX_SEGGRAM_MAX_K = {} is the limit".format(K, L.SEGGRAM_MAX_K))
+    out = torch.empty((G * K, W), dtype=torch.float32, device=S.device)
+    ws_bytes = lib.tfgx_segment_gram_workspace_bytes(N, G, K, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=S.device) if ws_bytes else None
+    L.check(lib.tfgx_segment_gram_f32(L.ptr(graph_plan.row_ptr), L.ptr(graph_plan.col), G, N, L.ptr(S), lds, K, L.ptr(Y), ldy, W,
+                                      L.ptr(out), max(W, 1), L.ptr(bad_flag), L.ptr(ws), ws_bytes, L.stream_ptr()),
+            "tfgx_segment_gram_f32")
+    return out
+
+
+def segment_gram_backward(node_graph_index, G, S, Y, g, need_s=True, need_y=True, bad_flag=None):
+    """One tfgx_segment_gram_backward_f32 call: (dS [N, K] or None, dY [N, W] or None) for the gradient g [G * K, W]."""
+    lib = L.require_gpu()
+    S, lds = L.row_major_2d(S)
+    Y, ldy = L.row_major_2d(Y)
+    g, ldg = L.row_major_2d(g)
+    N, K, W = int(S.shape[0]), int(S.shape[1]), int(Y.shape[1])
+    d_s = torch.empty((N, K), dtype=torch.float32, device=S.device) if need_s else None
+    d_y = torch.empty((N, W), dtype=torch.float32, device=S.device) if need_y else None
+    L.check(lib.tfgx_segment_gram_backward_f32(L.ptr(node_graph_index), N, G, L.ptr(S), lds, K, L.ptr(Y), ldy, W, L.ptr(g), ldg,
+                                               L.ptr(d_s), K, L.ptr(d_y), max(W, 1), L.ptr(bad_flag), L.stream_ptr()),
+            "tfgx_segment_gram_backward_f32")
+    return d_s, d_y
+
+
+class _SegmentGram(torch.autograd.Function):
+    """out[g] = S_g^T Y_g per graph (include/tfgx_seggram.h): one launch pair forward, one launch backward, which skips
+    whichever of dS / dY is not asked for.  When S and Y are the same tensor both gradients land on it (autograd adds them)."""
+
+    @staticmethod
+    def forward(ctx, graph_plan, node_graph_index, S, Y):
+        sd, yd = S.detach(), Y.detach()
+        ctx.graph_plan, ctx.ids = graph_plan, node_graph_index
+        ctx.save_for_backward(sd, yd)
+        return segment_gram_forward(graph_plan, sd, yd)
+
+    @staticmethod
+    def backward(ctx, g):
+        sd, yd = ctx.saved_tensors
+        need_s, need_y = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (need_s or need_y):
+            return None, None, None, None
+        d_s, d_y = segment_gram_backward(ctx.ids, ctx.graph_plan.n_dst, sd, yd, g.to(torch.float32), need_s, need_y)
+        return None, None, d_s, d_y
+
+
+def segment_gram(graph_plan, node_graph_index, S, Y):
+    """[G * K, W] block rows S_g^T Y_g for S [N, K] (K <= TFGX_SEGGRAM_MAX_K), Y [N, W]; graph_plan = the CSR over graphs of
+    node_graph_index (int32 [N] on the device, any order).  Differentiable in S and Y; bit-identical from run to run."""
+    S, Y = L.as_f32(S), L.as_f32(Y)
+    if needs_grad(S, Y):
+        return _SegmentGram.apply(graph_plan, node_graph_index, S, Y)
+    return segment_gram_forward(graph_plan, S, Y)

@@ -6,5 +6,5 @@ from .conv.graph_sage import MeanGraphSage, SumGraphSage, GCNGraphSage, MeanPool
 from .rnn import LSTM
 from .kernel.map_reduce import MapReduceGNN
 from .conv.propagation import GIN, SGC, TAGCN, APPNP, SSGC, ChebyNet, LEConv
-from .pool import CommonPool, MeanPool, SumPool, MaxPool, MinPool, SAGPool, SortPool, Set2Set, ASAP
+from .pool import CommonPool, MeanPool, SumPool, MaxPool, MinPool, SAGPool, SortPool, Set2Set, ASAP, DiffPool, MinCutPool
 from .sampling import DropEdge

@@ -6,3 +6,5 @@ from .sort_pool import sort_pool
 from .set2set import set2set
 from .cluster_pool import cluster_pool
 from .asap import asap
+from .diff_pool import diff_pool, diff_pool_coarsen
+from .min_cut_pool import min_cut_pool, min_cut_pool_coarsen, min_cut_pool_compute_losses

@@ -41,3 +41,21 @@ def min_pool(x, node_graph_index, num_graphs=None):
     """unsorted_segment_min = -max(-x); an empty graph holds float32 max (:48-52)."""
     x = L.as_f32(x)
     return -_pool(-x, node_graph_index, num_graphs, L.MAX)[2]
+
+
+CACHE_KEY_GRAPH_PLAN = "tfgx_set2set_graph_plan"
+
+
+def _graph_plan(ids, num_graphs, n, cache):
+    """The CSR over graphs (rows = graphs, col = node ids in stable order): built once per call.  With a `cache` it is kept
+    there together with the ids tensor it was built from (kept alive, so its address stays its own) and reused only for that
+    very storage, unmodified (same address, shape and version counter) and the same num_graphs; anything else rebuilds it.  Building synchronises once
+    (tfgx_build_csr_by_dst reports bad indices to the host)."""
+    hit = None if cache is None else cache.get(CACHE_KEY_GRAPH_PLAN)
+    if hit is not None and hit[0].data_ptr() == ids.data_ptr() and hit[0].shape == ids.shape and hit[1] == ids._version \
+            and hit[2].n_dst == num_graphs:
+        return hit[2]
+    plan = CsrPlan.build(torch.stack([ids, torch.arange(n, dtype=torch.int32, device=ids.device)]), num_graphs, max(n, 1))
+    if cache is not None:
+        cache[CACHE_KEY_GRAPH_PLAN] = (ids, ids._version, plan)
+    return plan

@@ -5,25 +5,8 @@ launch (tfgx_set2set_attend_f32: online softmax, x read once, only [G, F] writte
 import torch
 
 from ... import _lib as L
-from ...plan import CsrPlan
 from ... import autograd as AG
-
-CACHE_KEY_GRAPH_PLAN = "tfgx_set2set_graph_plan"
-
-
-def _graph_plan(ids, num_graphs, n, cache):
-    """The CSR over graphs (rows = graphs, col = node ids in stable order): built once per call.  With a `cache` it is kept
-    there together with the ids tensor it was built from (kept alive, so its address stays its own) and reused only for that
-    very storage, unmodified (same address, shape and version counter) and the same num_graphs; anything else rebuilds it.  Building synchronises once
-    (tfgx_build_csr_by_dst reports bad indices to the host)."""
-    hit = None if cache is None else cache.get(CACHE_KEY_GRAPH_PLAN)
-    if hit is not None and hit[0].data_ptr() == ids.data_ptr() and hit[0].shape == ids.shape and hit[1] == ids._version \
-            and hit[2].n_dst == num_graphs:
-        return hit[2]
-    plan = CsrPlan.build(torch.stack([ids, torch.arange(n, dtype=torch.int32, device=ids.device)]), num_graphs, max(n, 1))
-    if cache is not None:
-        cache[CACHE_KEY_GRAPH_PLAN] = (ids, ids._version, plan)
-    return plan
+from .common_pool import CACHE_KEY_GRAPH_PLAN, _graph_plan          # noqa: F401 - shared with the dense pooling layers
 
 
 def set2set(x, node_graph_index, lstm, num_iterations, training=None, num_graphs=None, batch_graphs=False, cache=None):
