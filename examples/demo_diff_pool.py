@@ -9,8 +9,9 @@ the data is the seeded NCI1-shaped stand-in of examples/demo_sag_pool_h.py.
     python examples/demo_diff_pool.py [--steps 40] [--graphs 600]
 
 Every S^T A S, S^T h product runs on the segmented-product kernel (include/tfgx_seggram.h); each pooled edge list carries its
-CSR plan, so the second level does not sort.  One difference from the reference: the pooled edge weights are detached before
-they enter the next level, because the GCN normalisation here takes no edge_weight that requires grad.
+CSR plan, so the second level does not sort.  As in the reference, the pooled edge weights are differentiable in the
+assignment and train through the second level's GCNs: the GCN normalisation differentiates an edge_weight that requires
+grad (include/tfgx_normgrad.h).
 """
 import argparse
 import os
@@ -53,8 +54,12 @@ class GcnStack(object):
 
 
 class DensePoolModel(object):
-    def __init__(self, pool_cls, num_features, num_classes, seed=0):
+    """detach_pooled_weights: hand the pooled edge weights to the next level as constants — for a pooling layer that refuses
+    an edge_weight that requires grad (MinCutPool); DiffPool trains through them."""
+
+    def __init__(self, pool_cls, num_features, num_classes, seed=0, detach_pooled_weights=False):
         dev = torch.device("cuda")
+        self.detach_pooled_weights = detach_pooled_weights
         self.gnns, self.pools = [], []
         for level, k in enumerate(NUM_CLUSTERS):
             f = num_features if level == 0 else UNITS
@@ -81,7 +86,8 @@ class DensePoolModel(object):
                 out, loss_func = out
                 losses.append(loss_func())
             h, edge_index, edge_weight, node_graph_index = out
-            edge_weight = edge_weight.detach()
+            if self.detach_pooled_weights:
+                edge_weight = edge_weight.detach()
             readouts.append(torch.cat([tfg.nn.mean_pool(h, node_graph_index, num_graphs),
                                        tfg.nn.max_pool(h, node_graph_index, num_graphs)], dim=-1))
         g = torch.cat(readouts, dim=-1)
@@ -91,7 +97,7 @@ class DensePoolModel(object):
         return (logits, losses) if return_losses else logits
 
 
-def run(pool_cls, with_losses, title):
+def run(pool_cls, with_losses, title, detach_pooled_weights=False):
     p = argparse.ArgumentParser(description=title)
     p.add_argument("--graphs", type=int, default=600)
     p.add_argument("--steps", type=int, default=40)
@@ -101,7 +107,8 @@ def run(pool_cls, with_losses, title):
     args = p.parse_args()
     torch.manual_seed(args.seed)
     data = make_dataset(args.graphs, args.seed)
-    model = DensePoolModel(pool_cls, data.num_features, data.num_classes, seed=args.seed)
+    model = DensePoolModel(pool_cls, data.num_features, data.num_classes, seed=args.seed,
+                           detach_pooled_weights=detach_pooled_weights)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     rng = np.random.Generator(np.random.PCG64(args.seed + 1))
     t0 = time.perf_counter()

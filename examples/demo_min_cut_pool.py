@@ -7,8 +7,9 @@ NCI1-shaped stand-in of examples/demo_sag_pool_h.py.
 
     python examples/demo_min_cut_pool.py [--steps 40] [--graphs 600]
 
-The pooled edge weights are detached before they enter the next level: MinCutPool normalises its edge weights with raw
-kernel launches and refuses an edge_weight that requires grad.
+Unlike the DiffPool demo, the pooled edge weights are detached before they enter the next level
+(detach_pooled_weights=True): MinCutPool normalises its edge weights with raw kernel launches (adj_norm_edge) and still
+refuses an edge_weight that requires grad, although the GCNs inside it would differentiate one.
 """
 import os
 import sys
@@ -19,4 +20,4 @@ import tf_geometric_amd as tfg   # noqa: E402
 from demo_diff_pool import run   # noqa: E402
 
 if __name__ == "__main__":
-    run(tfg.layers.MinCutPool, True, "MinCutPool on an NCI1-shaped synthetic set")
+    run(tfg.layers.MinCutPool, True, "MinCutPool on an NCI1-shaped synthetic set", detach_pooled_weights=True)

@@ -360,6 +360,16 @@ SEGGRAM_SIGNATURES = {
                                                       _I64, _P, _P]),
 }
 
+# include/tfgx_normgrad.h (the backward of the GCN normalisation: d/d raw edge weights): its own header, version and table —
+# checked against that header by tests/test_normgrad_abi.py.
+NORMGRAD_ABI_VERSION = 1
+NORMGRAD_ROW_PASS, NORMGRAD_COL_PASS, NORMGRAD_EDGE_PASS, NORMGRAD_ALL = 1, 2, 4, 7
+NORMGRAD_SIGNATURES = {
+    "tfgx_normgrad_version": (ctypes.c_int, []),
+    "tfgx_gcn_norm_backward_f32": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _P, _I32, _F32, _I32, _I32, _P, _P, _P, _P,
+                                                  _P, _P, _I32, _P]),
+}
+
 _lib = None
 
 
@@ -415,6 +425,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in NORMGRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_normgrad_version() != NORMGRAD_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_normgrad ABI {} but this package binds {} "
+                        "(include/tfgx_normgrad.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_normgrad_version(), NORMGRAD_ABI_VERSION))
     if lib.tfgx_seggram_version() != SEGGRAM_ABI_VERSION or lib.tfgx_seggram_block() != SEGGRAM_BLOCK:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_seggram ABI {} (block {}) but this package binds {} (block {}) "
                         "(include/tfgx_seggram.h): rebuild with __graft_entry__.build()".format(

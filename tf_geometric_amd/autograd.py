@@ -19,6 +19,8 @@ C-ABI kernel launches:
   linear (x @ W + b, relu)          forward = tfgx_gemm_bias_act_f32; d/dx = the same kernel on W^T (tfgx_transpose_f32);
                                     d/dW, d/db = tfgx_gemm_tn_f32 (MFMA reduction over the node dimension)
   segment_softmax                   forward = tfgx_edge_softmax_f32; backward = out * (g - segsum(out * g)) on the segment kernel
+  gcn_norm (tracked edge weights)   forward = the two normalisation kernels on detached data; backward wrt the raw weights =
+                                    tfgx_gcn_norm_backward_f32 (row pass, column pass over the transposed plan, edge pass)
 
 The functional API (nn/conv/*.py) routes through these only when torch.is_grad_enabled() and an input requires
 grad; inference keeps the fused single-launch paths.
@@ -1605,3 +1607,91 @@ def segment_gram(graph_plan, node_graph_index, S, Y):
     if needs_grad(S, Y):
         return _SegmentGram.apply(graph_plan, node_graph_index, S, Y)
     return segment_gram_forward(graph_plan, S, Y)
+
+
+def gcn_norm_forward(plan, w, tw, col_degrees, norm, fill, diag, add_self_loop, renorm):
+    """The two launches of the GCN normalisation (tfgx_segment_weight_sum_f32, tfgx_gcn_norm_edges_f32) on constants:
+    (w_out[E] in CSR order, self_coef[n], row_deg, col_deg).  w: raw weights in CSR order or None (unweighted).
+    col_degrees: the column degrees are wanted too (norm="both", sym=False), summed from tw = the same weights in the
+    transposed plan's order (None with w); col_deg is None otherwise."""
+    lib = L.require_gpu()
+    n = plan.n_dst
+    dev = plan.row_ptr.device
+    row_deg = torch.empty(n, dtype=torch.float32, device=dev)
+    L.check(lib.tfgx_segment_weight_sum_f32(L.ptr(plan.row_ptr), L.ptr(w), n, diag, L.ptr(row_deg), L.stream_ptr()),
+            "tfgx_segment_weight_sum_f32")
+    col_deg = None
+    if col_degrees:
+        tplan = plan.transposed()
+        col_deg = torch.empty(tplan.n_dst, dtype=torch.float32, device=dev)
+        L.check(lib.tfgx_segment_weight_sum_f32(L.ptr(tplan.row_ptr), L.ptr(tw), tplan.n_dst, diag, L.ptr(col_deg),
+                                                L.stream_ptr()), "tfgx_segment_weight_sum_f32")
+    w_out = torch.empty(plan.num_edges, dtype=torch.float32, device=dev)
+    self_coef = torch.empty(n, dtype=torch.float32, device=dev)
+    L.check(lib.tfgx_gcn_norm_edges_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), L.ptr(w), n, L.ptr(row_deg),
+                                        L.ptr(col_deg), L.NORM_MODES[norm], fill, int(bool(add_self_loop)),
+                                        int(bool(renorm)), L.ptr(w_out), L.ptr(self_coef), L.stream_ptr()),
+            "tfgx_gcn_norm_edges_f32")
+    return w_out, self_coef, row_deg, col_deg
+
+
+def gcn_norm_backward(plan, w, row_deg, col_deg, norm, fill, add_self_loop, renorm, G, S, passes=L.NORMGRAD_ALL,
+                      scratch=None):
+    """d/dw (CSR order) of gcn_norm_forward given G = d/dw_out and S = d/dself_coef (None: no such gradient): the three
+    launches of tfgx_gcn_norm_backward_f32 (include/tfgx_normgrad.h) — segmented sums over the plan and over the transposed
+    plan in a fixed order, no atomics, no host synchronisation.  passes / scratch = (A, B, t, dw) of an earlier call: one
+    launch alone on what that call left (tools/bench_gcn_norm_grad.py)."""
+    lib = L.require_gpu()
+    E = plan.num_edges
+    dev = w.device
+    if E == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    mode = L.NORM_MODES[norm]
+    n_rows, n_cols = plan.n_dst, plan.n_src
+    pt, t2d = _transposed(plan) if mode != L.NORM_LEFT else (None, None)
+    if scratch is None:
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)      # noqa: E731
+        scratch = (new(n_rows) if mode != L.NORM_RIGHT else None, new(n_cols) if pt is not None else None,
+                   new(E) if pt is not None else None, new(E))
+    A, B, t, dw = scratch
+    L.check(lib.tfgx_gcn_norm_backward_f32(
+        L.ptr(plan.row_ptr), L.ptr(plan.col), L.ptr(w), n_rows, n_cols, None if pt is None else L.ptr(pt.row_ptr), L.ptr(t2d),
+        L.ptr(row_deg), L.ptr(col_deg), mode, fill, int(bool(add_self_loop)), int(bool(renorm)), L.ptr(G), L.ptr(S),
+        L.ptr(A), L.ptr(B), L.ptr(t), L.ptr(dw), int(passes), L.stream_ptr()), "tfgx_gcn_norm_backward_f32")
+    return dw
+
+
+class _GcnNorm(torch.autograd.Function):
+    """(w_out, self_coef) = the GCN normalisation of the raw weights w (CSR order): the forward is gcn_norm_forward on
+    detached data — the bits of the untracked route — and the backward is tfgx_gcn_norm_backward_f32.  A factor the forward
+    zeroed (the degree power was inf or NaN) has derivative zero, so the gradient of an isolated node's edges is finite."""
+
+    @staticmethod
+    def forward(ctx, plan, w, norm, sym, fill, diag, add_self_loop, renorm):
+        wd = w.detach().contiguous()
+        both_sides = norm == "both" and not sym
+        tw = (_permute(wd, _transposed(plan)[1]) if plan.num_edges else wd) if both_sides else None
+        w_out, self_coef, row_deg, col_deg = gcn_norm_forward(plan, wd, tw, both_sides, norm, fill, diag, add_self_loop, renorm)
+        ctx.plan, ctx.cfg = plan, (norm, fill, add_self_loop, renorm)
+        ctx.save_for_backward(wd, row_deg, col_deg)
+        ctx.set_materialize_grads(False)
+        return w_out, self_coef
+
+    @staticmethod
+    def backward(ctx, G, S):
+        wd, row_deg, col_deg = ctx.saved_tensors
+        norm, fill, add_self_loop, renorm = ctx.cfg
+        if S is not None and not add_self_loop:
+            S = None        # the coefficient is the constant 0 there
+        if G is None and S is None:
+            return (None,) * 8
+        G = torch.zeros_like(wd) if G is None else L.as_f32(G).contiguous()
+        S = None if S is None else L.as_f32(S).contiguous()
+        dw = gcn_norm_backward(ctx.plan, wd, row_deg, col_deg, norm, fill, add_self_loop, renorm, G, S)
+        return None, dw, None, None, None, None, None, None
+
+
+def gcn_norm(plan, w, norm, sym, fill, diag, add_self_loop, renorm):
+    """Differentiable GCN normalisation of tracked raw weights w (CSR order, e.g. from edge_attr_csr):
+    (w_out, self_coef), both carrying the gradient to w."""
+    return _GcnNorm.apply(plan, w, norm, bool(sym), float(fill), float(diag), bool(add_self_loop), bool(renorm))

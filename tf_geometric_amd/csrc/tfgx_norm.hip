@@ -20,6 +20,9 @@ __device__ __forceinline__ float group_sum(float v)
 
 constexpr int kLongRow = 2048;             // edges: longer rows are walked by the whole workgroup
 constexpr int kRowsPerBlock = kBlock / NG;
+// a PRIME grid cap: with 8192 workgroups one workgroup's 32-row tiles start at multiples of 2^18, where an R-MAT graph keeps its
+// hubs (ids with few one-bits), and that workgroup walked them all (tfgx_normgrad.hip kGridCap; no sum depends on the grid)
+constexpr int kGridCap = 8191;
 
 __global__ __launch_bounds__(kBlock) void weight_sum_kernel(const int32_t* __restrict__ row_ptr,
                                                             const float* __restrict__ w, int64_t n, float diag,
@@ -162,7 +165,7 @@ extern "C" int tfgx_segment_weight_sum_f32(const int32_t* row_ptr, const float* 
     TFGX_REQUIRE(n >= 0, "negative n");
     if (n == 0) return TFGX_OK;
     TFGX_REQUIRE(row_ptr && deg, "null pointer");
-    weight_sum_kernel<<<grid_for(n, kRowsPerBlock), kBlock, 0, as_stream(stream)>>>(row_ptr, w, n, diag, deg);
+    weight_sum_kernel<<<grid_for(n, kRowsPerBlock, kGridCap), kBlock, 0, as_stream(stream)>>>(row_ptr, w, n, diag, deg);
     TFGX_LAUNCH_CHECK("weight_sum_kernel");
     return TFGX_OK;
 }
@@ -177,7 +180,7 @@ extern "C" int tfgx_gcn_norm_edges_f32(const int32_t* row_ptr, const int32_t* co
     TFGX_REQUIRE(norm_mode >= TFGX_NORM_BOTH && norm_mode <= TFGX_NORM_RIGHT, "bad norm mode");
     if (n == 0) return TFGX_OK;
     TFGX_REQUIRE(row_ptr && row_deg && self_coef, "null pointer");  // col / w_out may be null when E == 0
-    gcn_norm_kernel<<<grid_for(n, kRowsPerBlock), kBlock, 0, as_stream(stream)>>>(
+    gcn_norm_kernel<<<grid_for(n, kRowsPerBlock, kGridCap), kBlock, 0, as_stream(stream)>>>(
         row_ptr, col, w, n, row_deg, col_deg, norm_mode, fill, add_self_loop, renorm, w_out, self_coef);
     TFGX_LAUNCH_CHECK("gcn_norm_kernel");
     return TFGX_OK;

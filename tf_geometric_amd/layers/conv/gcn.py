@@ -3,6 +3,7 @@
 import warnings
 
 from ..._lib import as_f32
+from ...autograd import needs_grad
 from ...nn.conv.gcn import gcn, gcn_build_cache_for_graph, gcn_build_cache_by_adj
 from ...sparse import SparseMatrix
 from ...plan import CACHE_KEY_PLAN
@@ -76,7 +77,10 @@ class GCN(Layer):
             edge_weight = inputs[2] if len(inputs) == 3 else None
             num_nodes = int(x.shape[0])
             key = "tfgx_gcn_adj"
-            sparse_adj = cache.get(key) if cache is not None else None
+            # an edge_weight being trained is this step's value: its matrix is built afresh and never stored (a stored one
+            # would serve one step's weights as constants); the CSR plan is the graph's and is shared as ever
+            tracked = needs_grad(edge_weight)
+            sparse_adj = cache.get(key) if (cache is not None and not tracked) else None
             if sparse_adj is None:
                 sparse_adj = SparseMatrix(edge_index, value=edge_weight, shape=[num_nodes, num_nodes])
                 if cache is not None:
@@ -84,7 +88,8 @@ class GCN(Layer):
                         sparse_adj._plan = cache[CACHE_KEY_PLAN]
                     else:
                         cache[CACHE_KEY_PLAN] = sparse_adj.plan
-                    cache[key] = sparse_adj
+                    if not tracked:
+                        cache[key] = sparse_adj
         from ...plan import HalfRows
         x_in = x if (isinstance(x, (SparseMatrix, HalfRows)) or getattr(x, "is_sparse", False)) else as_f32(x)   # sparse x: :269-270; a HalfRows: gcn() takes it when the layer aggregates x itself
         return gcn(x_in, sparse_adj, self.kernel, self.bias, activation=self.activation,

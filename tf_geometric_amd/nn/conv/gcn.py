@@ -70,8 +70,15 @@ class NormedAdj(object):
 
 
 def gcn_norm_adj(sparse_adj, norm="both", add_self_loop=True, sym=True, renorm=True, improved=False, cache=None):
-    """Normalised adjacency for GCN (reference: gcn.py:32-130; same arguments, same cache key)."""
-    lib = L.require_gpu()
+    """Normalised adjacency for GCN (reference: gcn.py:32-130; same arguments, same cache key).
+
+    Edge weights that require grad (with grad mode on) are differentiated: the same two kernels run on the detached weights
+    and autograd.gcn_norm records their backward, so w_csr / self_coef carry the gradient to sparse_adj.value in the caller's
+    edge order.  Such a result is one step's, not the graph's: it is neither read from nor written to `cache`."""
+    L.require_gpu()
+    tracked = sparse_adj._has_value and AG.needs_grad(sparse_adj.value)
+    if tracked:
+        cache = None
     if cache is not None:
         cache_key = compute_cache_key(norm, add_self_loop, sym, renorm, improved)
         cached = cache.get(cache_key, None)
@@ -91,29 +98,18 @@ def gcn_norm_adj(sparse_adj, norm="both", add_self_loop=True, sym=True, renorm=T
         raise Exception("norm='right' indexes the row degrees by column id: sparse_adj.shape[1] must not exceed "
                         "sparse_adj.shape[0]")
     plan = sparse_adj.plan
-    n = plan.n_dst
-    dev = plan.row_ptr.device
-    w = sparse_adj.value_csr if sparse_adj._has_value else None
     if norm == "both":
         diag = fill_weight if (add_self_loop and renorm) else 0.0                                 # :76-77
     else:
         diag = fill_weight if add_self_loop else 0.0                                              # :71-72
-    row_deg = torch.empty(n, dtype=torch.float32, device=dev)
-    L.check(lib.tfgx_segment_weight_sum_f32(L.ptr(plan.row_ptr), L.ptr(w), n, diag, L.ptr(row_deg), L.stream_ptr()),
-            "tfgx_segment_weight_sum_f32")
-    col_deg = None
-    if norm == "both" and not sym:                                                                # :88-91
-        tplan = plan.transposed()
-        tw = tplan.edge_attr_to_csr(sparse_adj.value) if sparse_adj._has_value else None
-        col_deg = torch.empty(tplan.n_dst, dtype=torch.float32, device=dev)
-        L.check(lib.tfgx_segment_weight_sum_f32(L.ptr(tplan.row_ptr), L.ptr(tw), tplan.n_dst, diag, L.ptr(col_deg),
-                                                L.stream_ptr()), "tfgx_segment_weight_sum_f32")
-    w_out = torch.empty(plan.num_edges, dtype=torch.float32, device=dev)
-    self_coef = torch.empty(n, dtype=torch.float32, device=dev)
-    L.check(lib.tfgx_gcn_norm_edges_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), L.ptr(w), n, L.ptr(row_deg),
-                                        L.ptr(col_deg), L.NORM_MODES[norm], fill_weight, int(bool(add_self_loop)),
-                                        int(bool(renorm)), L.ptr(w_out), L.ptr(self_coef), L.stream_ptr()),
-            "tfgx_gcn_norm_edges_f32")
+    both_sides = norm == "both" and not sym                                                       # :88-91
+    if tracked:
+        w_out, self_coef = AG.gcn_norm(plan, AG.edge_attr_csr(plan, sparse_adj.value), norm, sym, fill_weight, diag,
+                                       add_self_loop, renorm)
+    else:
+        w = sparse_adj.value_csr if sparse_adj._has_value else None
+        tw = plan.transposed().edge_attr_to_csr(sparse_adj.value) if (both_sides and sparse_adj._has_value) else None
+        w_out, self_coef, _, _ = AG.gcn_norm_forward(plan, w, tw, both_sides, norm, fill_weight, diag, add_self_loop, renorm)
     normed = NormedAdj(plan, w_out, self_coef if add_self_loop else None, list(sparse_adj.shape))
     if cache is not None:
         cache[cache_key] = normed                                                                 # :125-128
@@ -198,7 +194,10 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     normed = normed.dropout(edge_drop_rate, training=training)                                    # :262
     x = x if half else L.as_f32(x)
     act, post = _resolve_act(activation)
-    if AG.needs_grad(x, kernel, bias):      # training: differentiable un-fused route (autograd.py)
+    # training: differentiable un-fused route (autograd.py) — also for a tracked edge_weight under frozen x and kernel, whose
+    # gradient arrives through the normalised weights (d/dw_csr: the SDDMM, d/dself_coef) and gcn_norm_adj's backward
+    tracked_adj = AG.needs_grad(normed.w_csr, normed.self_coef)
+    if tracked_adj or AG.needs_grad(x, kernel, bias):
         narrow_first = kernel is not None and int(x.shape[1]) < int(kernel.shape[1])
         h = x if (kernel is None or narrow_first) else AG.linear(x, kernel, gathered=True)
         # raw input features: static across epochs
@@ -206,7 +205,8 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
         # bias + ReLU ride in the LAST kernel's epilogue (GEMM when the aggregation ran first, else the aggregation)
         bias_t = None if bias is None else L.as_f32(bias)
         if narrow_first:
-            pre = static_aggregate(h, normed.plan, layouts, L.SUM, normed.w_csr, normed.self_coef)   # opt-in memo (layer 0)
+            # opt-in memo (layer 0): constants only — never consulted for tracked weights
+            pre = None if tracked_adj else static_aggregate(h, normed.plan, layouts, L.SUM, normed.w_csr, normed.self_coef)
             fused = None
             if pre is None:
                 # ONE forward launch (tfgx_aggregate_gemm_f32), on the static feature layout when x has one; the aggregate is
