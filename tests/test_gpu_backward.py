@@ -1030,7 +1030,8 @@ def test_pool_mlp_max_weight_gradient_from_destination_rows(tfg, oracle, f_in, u
     assert lib.tfgx_pool_mlp_max_wgrad_applies(f_in, 4 * ku)
     out_f, g_f = run(True)
     out_c, g_c = run(False)
-    assert torch.equal(out_f, out_c)
+    # bit for bit: row 7 pools float32 lowest, its projection overflows to inf - inf, and the ReLU epilogue keeps that NaN
+    assert torch.equal(out_f.view(torch.int32), out_c.view(torch.int32))
     for k in ws:
         scale = float(g_c[k].abs().max()) + 1.0
         assert float((g_f[k] - g_c[k]).abs().max()) <= 2e-5 * scale, k

@@ -403,3 +403,52 @@ def test_partial_plan_launch_leaves_hub_rows_past_n_dst_alone(tfg):
         assert_parity(out[:k].cpu().numpy(), whole[:k].cpu().numpy(), what="first rows of the plan")
     finally:
         P.HUB_THRESHOLD, P.HUB_CHUNK = old
+
+
+@pytest.mark.parametrize("route", ["gemm", "segment_reduce", "gat"])
+def test_relu_epilogue_keeps_nan(tfg, route):
+    """Found by test_gpu_nonfinite.py: apply_act was fmaxf(v, 0), which returns 0 for a NaN — a NaN from a diverged layer left
+    the next ReLU epilogue as a clean zero.  ReLU keeps NaN, sends -inf to 0 and keeps +inf (np.maximum(h, 0) of the oracle)."""
+    from tf_geometric_amd import plan as P
+    from tf_geometric_amd.nn.conv.gat import gat_attention
+    L = tfg._lib
+    vals = torch.tensor([float("nan"), float("-inf"), float("inf")], device="cuda")
+    want = np.array([np.nan, 0.0, np.inf], np.float32)
+    plan = P.CsrPlan.build(L.as_i32(np.array([[0, 1, 2], [0, 1, 2]], np.int32)), 3, 3)
+    if route == "gemm":
+        bias = torch.ones(5, device="cuda")
+        bias[:3] = vals
+        got = P.gemm_bias_act(torch.ones(5, 4, device="cuda"), torch.ones(4, 5, device="cuda"), bias=bias, act=L.ACT_RELU).t()
+    elif route == "segment_reduce":
+        x = torch.ones(3, 5, device="cuda")
+        x[:, 0] = vals
+        got = P.segment_reduce(plan, x, L.SUM, act=L.ACT_RELU)
+    else:
+        v = torch.ones(3, 4, device="cuda")
+        v[:, 0] = vals
+        got = gat_attention(plan, torch.ones(3, 1, device="cuda"), torch.ones(3, 1, device="cuda"), v, 1, add_self_loop=False,
+                            act=L.ACT_RELU)
+    got = got.cpu().numpy()
+    rest = got[3:] if route == "gemm" else got[:, 1:]          # (gemm: got = C^T, the planted bias entries are columns 0..2 of C)
+    assert np.array_equal(got[:3, 0], want, equal_nan=True), (route, got[:3, 0])
+    assert (rest > 0).all() and np.isfinite(rest).all(), route + ": a neighbouring column was reached"
+
+
+def test_max_row_of_only_neg_inf_messages_is_an_empty_row(tfg):
+    """Decision ("Non-finite values"), found by test_gpu_nonfinite.py: TFGX_MAX is max(float32 lowest, messages), so a
+    row whose messages in a column are all -inf returns the empty row's value, and its packed winner entry has a tie count of 0
+    (no edge holds the maximum; the backward gives it no gradient).  A -inf beside a finite message is an ordinary loser."""
+    from tf_geometric_amd import plan as P
+    L = tfg._lib
+    ei = np.array([[0, 1, 1], [0, 0, 1]], np.int32)            # row 0 <- {0}; row 1 <- {0, 1}; row 2 empty
+    plan = P.CsrPlan.build(L.as_i32(ei), 3, 2)
+    x = torch.ones(2, 32, device="cuda")
+    x[0, 5] = float("-inf")
+    pk = torch.full((3, 32), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
+    out = P.segment_reduce(plan, x, L.MAX, track=pk).cpu().numpy()
+    pk = pk.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    lowest = np.float32(-3.4028234663852886e38)
+    assert out[0, 5] == lowest and out[2, 5] == lowest and out[1, 5] == 1.0, out[:, 5]
+    assert pk[0, 5] >> 16 == 0 and pk[2, 5] == 0xFFFF, [hex(int(v)) for v in pk[:, 5]]
+    assert pk[1, 5] == (1 << 16) | 1                           # the finite message of source 1, at position 1 of the row
+    assert (out[:2, :5] == 1.0).all() and (out[:2, 6:] == 1.0).all() and (pk[0, :5] == (1 << 16)).all() and (pk[1, 6:] == (2 << 16)).all()

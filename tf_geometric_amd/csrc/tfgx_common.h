@@ -65,7 +65,8 @@ inline int grid_for(int64_t work_items, int per_block, int cap = kMaxGrid)
     return static_cast<int>(g);
 }
 
-__device__ __forceinline__ float apply_act(float v, int act) { return (act == TFGX_ACT_RELU) ? fmaxf(v, 0.0f) : v; }
+// ReLU keeps a NaN (fmaxf alone returns the other operand, 0); every other input gives fmaxf's bits
+__device__ __forceinline__ float apply_act(float v, int act) { return (act == TFGX_ACT_RELU && v == v) ? fmaxf(v, 0.0f) : v; }
 
 // ---- vector load/store helpers shared by the streaming kernels (VEC floats per lane: 4 -> global_load_dwordx4)
 template <int VEC> struct VecT;
