@@ -235,8 +235,9 @@ def test_plain_16_bit_tensor_still_takes_the_float32_kernel(tfg, monkeypatch):
     plan = P.CsrPlan.build(L.as_i32(ei), 50, 50)
     xb = torch.randn(50, 64, device="cuda").to(torch.bfloat16)
     half_launches = []
-    real = P._segment_reduce_h16
-    monkeypatch.setattr(P, "_segment_reduce_h16", lambda *a, **k: (half_launches.append(1), real(*a, **k))[1])
+    lib = L.require_gpu()
+    real = lib.tfgx_segment_reduce_h16      # counted at the library entry: whatever Python path leads there
+    monkeypatch.setattr(lib, "tfgx_segment_reduce_h16", lambda *a: (half_launches.append(1), real(*a))[1])
     a = tfg.nn.aggregate_neighbors(xb, L.as_i32(ei), updater=tfg.nn.identity_updater)
     assert not half_launches, "a plain 16-bit tensor reached tfgx_segment_reduce_h16"
     b = tfg.nn.aggregate_neighbors(xb.float(), L.as_i32(ei), updater=tfg.nn.identity_updater)

@@ -441,76 +441,6 @@ def h16_friendly_ld(F):
     return best
 
 
-def _segment_reduce_h16(plan, h, op, w_csr, out, act, self_coef, bias, add_x, accumulate, mean_count, row_begin, row_end,
-                        rp_stride, col, n_dst, describe, wide_blocks, out_dtype):
-    """segment_reduce on a HalfRows: one launch of tfgx_segment_reduce_h16.  The verified / promoted-layout machinery is not
-    consulted; hub lists and the walk order come from the plan exactly as for float32."""
-    lib = L.require_gpu()
-    F = h.F
-    n_dst = plan.n_dst if n_dst is None else int(n_dst)
-    if out_dtype is not None and out_dtype not in L.H16_DTYPES and out_dtype != torch.float32:
-        raise TypeError("segment_reduce: out_dtype must be None, torch.float32, torch.bfloat16 or torch.float16")
-    half_out = out_dtype in L.H16_DTYPES
-    given = out is not None
-    if half_out:
-        if out is None:
-            out = HalfRows.empty(n_dst, F, out_dtype, h.device)
-        assert isinstance(out, HalfRows) and out.dtype == out_dtype and out.F == F, "out must be a HalfRows of out_dtype"
-        out_ptr, ldo = out.table.data_ptr(), out.ld
-    else:
-        if out is None:
-            out = torch.empty((n_dst, F), dtype=torch.float32, device=h.device)
-        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == h.device and out.dim() == 2
-                and int(out.shape[0]) >= n_dst and int(out.shape[1]) == F):
-            raise TypeError("segment_reduce on a HalfRows: out must be a float32 [n_dst, F] tensor on the table's device "
-                            "(or a HalfRows with out_dtype=)")
-        out2, ldo = L.row_major_2d(out)
-        assert out2 is out, "out must be row-major"
-        out_ptr = out.data_ptr()
-    a = L.ReduceArgs()
-    rb = plan.row_ptr if row_begin is None else row_begin
-    re = plan.row_ptr[1:] if row_end is None else row_end
-    a.row_begin, a.row_end, a.rp_stride = rb.data_ptr(), re.data_ptr(), rp_stride
-    a.col = (plan.col if col is None else col).data_ptr()
-    a.w = 0 if w_csr is None else w_csr.data_ptr()
-    a.n_dst = n_dst
-    a.x, a.ldx, a.F = h.table.data_ptr(), h.ld, F
-    a.out, a.ldo = out_ptr, ldo
-    a.op, a.act, a.accumulate = op, act, 1 if accumulate else 0
-    a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
-    a.bias = 0 if bias is None else bias.data_ptr()
-    if add_x is not None:
-        add_x, ld_add = L.row_major_2d(add_x)
-        a.add_x, a.ld_add = add_x.data_ptr(), ld_add
-    a.mean_count = 0 if mean_count is None else mean_count.data_ptr()
-    explicit = row_begin is not None or row_end is not None or col is not None
-    if not explicit and n_dst == plan.n_dst and USE_ROW_ORDER and F <= ROW_ORDER_MAX_F:
-        order = plan.row_order()
-        if order is not None:
-            a.row_order = order.data_ptr()
-    hub = plan.hub_info() if (not explicit and n_dst == plan.n_dst) else None
-    if hub is not None:
-        hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
-        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=h.device)
-        a.hub_threshold = plan.hub_threshold
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
-        a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
-        a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
-        a.hub_scratch = scratch.data_ptr()
-    a.wide_blocks = h16_wide_blocks_hint(explicit, hub is not None, plan.num_edges, n_dst) if wide_blocks is None else int(wide_blocks)
-    xdt = L.H16_DTYPES[h.dtype]
-    odt = L.H16_DTYPES[out_dtype] if half_out else L.DT_F32
-    if describe:
-        buf = ctypes.create_string_buffer(160)
-        L.check(lib.tfgx_segment_reduce_h16_describe(ctypes.byref(a), xdt, odt, buf, 160), "tfgx_segment_reduce_h16_describe")
-        return buf.value.decode()
-    L.check(lib.tfgx_segment_reduce_h16(ctypes.byref(a), xdt, odt, L.stream_ptr()), "tfgx_segment_reduce_h16")
-    _AGG_LAUNCHES[0] += 1
-    if given and not half_out:
-        written_by_kernel(out)
-    return out
-
-
 H16_WIDE_BLOCKS = True       # column blocks on wide 16-bit rows without hub lists: 14 % faster at F = 256 / 512 (profiles/h16_products.jsonl)
 
 
@@ -1027,116 +957,173 @@ def wide_blocks_hint(explicit_spans, has_hub_lists, ldx, num_edges, n_rows):
     return 0
 
 
-def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=None, bias=None, add_x=None,
-                   accumulate=False, mean_count=None, row_begin=None, row_end=None, rp_stride=1, col=None,
-                   n_dst=None, describe=False, track=None, track_row_begin=None, wide_blocks=None, out_dtype=None):
-    """One launch of tfgx_segment_reduce_f32 on `plan` (or on explicit row_begin/row_end/col views of it).
-    `x` is a dense [n_src, F] tensor or a SplitRows.  describe=True launches nothing and returns the kernel symbol the
-    dispatcher picks for these arguments (tfgx_segment_reduce_describe).  `track` (TFGX_MAX, training forward): int32
-    [n_dst, F] that receives tie count << 16 | row-relative position of the first maximal edge (tfgx_reduce_args.track;
-    see can_track); with accumulate=True the launch merges into the (out, track) earlier launches stored for earlier
-    sub-spans of the same rows (track_row_begin: the first position of the whole row).
-    `x` may also be a HalfRows (a 16-bit table): the launch is tfgx_segment_reduce_h16, float32 arithmetic, the float32
-    route's bits; out_dtype = torch.bfloat16 / torch.float16 then returns the result as a HalfRows (rounded as the last step)."""
-    if isinstance(x, HalfRows):
-        if track is not None or track_row_begin is not None:
-            raise L.TfgxError("tfgx_segment_reduce_h16: track: not supported on a 16-bit table (max aggregation is inference-only)")
-        return _segment_reduce_h16(plan, x, op, w_csr, out, act, self_coef, bias, add_x, accumulate, mean_count, row_begin,
-                                   row_end, rp_stride, col, n_dst, describe, wide_blocks, out_dtype)
-    if out_dtype not in (None, torch.float32):
-        raise TypeError("segment_reduce: out_dtype needs a HalfRows input")
-    lib = L.require_gpu()
-    split = x if isinstance(x, SplitRows) else None
-    verified = None
-    if (split is None and row_begin is None and row_end is None and col is None and track is None and not accumulate
-            and (n_dst is None or int(n_dst) == plan.n_dst)):
-        verified = verified_layout(plan, x, describe=describe)      # a promoted table: served from its layout, checked
-        if verified is not None:
-            table, split = x, verified.rows
-    if split is not None:
-        x, ldx = L.row_major_2d(split.main)
-        F = split.shape[1]
-    else:
-        x, ldx = L.row_major_2d(x)
-        F = int(x.shape[1])
-        if row_begin is None and row_end is None and col is None:
-            x, ldx = relaid_for_gather(x, ldx, plan.hub_info() is not None, dry_run=describe)
-    n_dst = plan.n_dst if n_dst is None else int(n_dst)
-    given = out is not None
-    if out is None:
-        out = torch.empty((n_dst, F), dtype=torch.float32, device=x.device)
-    out2, ldo = L.row_major_2d(out)
-    assert out2 is out, "out must be row-major"
+def _reduce_args(plan, x_ptr, ldx, F, op, w_csr, n_dst=None, row_begin=None, row_end=None, rp_stride=1, col=None,
+                 act=L.ACT_NONE, accumulate=False, self_coef=None, bias=None, add_x=None, mean_count=None,
+                 row_order=None, hub=None, hub_order_slot=None):
+    """The one place plan.py fills a tfgx_reduce_args: what every launch derives from the plan (spans — row_ptr / row_ptr[1:]
+    unless given —, col, w, n_dst), the table as (x_ptr, ldx, F) and the common operands.  The walk order, the hub lists
+    (`hub` = plan.hub_info(); they get a fresh float32 scratch [n_hub_chunks, F]) and hub_order_slot are attached when the
+    caller passes them: which launch takes them is the caller's decision, there is no policy here.  Members only some
+    launches have (out / ldo, the split layout, verify, track, wide_blocks) are the caller's.
+    Returns (args, keep): `keep` holds the tensors the struct names by address and nothing else refers to — the row-major
+    add_x, the scratch — and must stay referenced until the launch has been enqueued (the plan and the caller hold the rest)."""
     a = L.ReduceArgs()
-    rb = plan.row_ptr if row_begin is None else row_begin
-    re = plan.row_ptr[1:] if row_end is None else row_end
-    a.row_begin = rb.data_ptr()
-    a.row_end = re.data_ptr()
+    a.row_begin = (plan.row_ptr if row_begin is None else row_begin).data_ptr()
+    # (the address of plan.row_ptr[1:] — int32, unit stride — without building that view on every call)
+    a.row_end = plan.row_ptr.data_ptr() + 4 if row_end is None else row_end.data_ptr()
     a.rp_stride = rp_stride
-    c = plan.col if col is None else col
-    a.col = c.data_ptr()
+    a.col = (plan.col if col is None else col).data_ptr()
     a.w = 0 if w_csr is None else w_csr.data_ptr()
-    a.n_dst = n_dst
-    a.x = x.data_ptr()
-    a.ldx = ldx
-    a.F = F
-    a.out = out.data_ptr()
-    a.ldo = ldo
-    a.op = op
-    a.act = act
-    a.accumulate = 1 if accumulate else 0
+    a.n_dst = plan.n_dst if n_dst is None else n_dst
+    a.x, a.ldx, a.F = x_ptr, ldx, F
+    a.op, a.act, a.accumulate = op, act, 1 if accumulate else 0
     a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
     a.bias = 0 if bias is None else bias.data_ptr()
+    scratch = None
     if add_x is not None:
         add_x, ld_add = L.row_major_2d(add_x)
-        a.add_x = add_x.data_ptr()
-        a.ld_add = ld_add
+        a.add_x, a.ld_add = add_x.data_ptr(), ld_add
     a.mean_count = 0 if mean_count is None else mean_count.data_ptr()
-    if split is not None:
-        a.x_tail, a.ld_tail, a.f_main = split.tail.data_ptr(), int(split.tail.shape[1]), int(split.main.shape[1])
-        if split.edge_tail is not None and split.edge_plan is plan and col is None:
-            a.edge_tail, a.ld_edge_tail = split.edge_tail.data_ptr(), int(split.edge_tail.shape[1])
-    if verified is not None:
-        a.verify, a.verify_x, a.ld_verify_x = 1, table.data_ptr(), int(table.stride(0))
-        a.n_verify, a.verify_word = int(table.shape[0]), verified.word.data_ptr()
-    if row_begin is None and row_end is None and col is None and n_dst == plan.n_dst and USE_ROW_ORDER and F <= ROW_ORDER_MAX_F:
-        # skewed plans: degree-ordered walk (the rows sharing a wave have similar lengths).  Same-box A/B on R-MAT graphs:
-        # F = 20: -7 .. -16 %, F = 64: -4 .. -11 % (round 2); round 4, after the hub finalize stopped being a latency chain
-        # (profiles/r04_ab_row_order.jsonl, 2.4 M / 123 M and 2^21 / 61 M edges): F = 100: -10 / -11 %, F = 128: -3 / -5 %,
-        # F = 256: -2 .. +1 % (one row per wave there: nothing to balance) — hence the width limit
-        order = plan.row_order()
-        if order is not None:
-            a.row_order = order.data_ptr()
-    if track is not None:
-        a.track, a.ld_track = track.data_ptr(), int(track.stride(0))
-        if track_row_begin is not None:      # positions relative to the WHOLE row when it is reduced span by span
-            a.track_row_begin = track_row_begin.data_ptr()
-    # (a launch over the first rows of a larger plan takes no hub lists: they name rows of the WHOLE plan, and the finalize
-    # pass would write the rows past n_dst; long rows are then walked inline — same sums)
-    hub = plan.hub_info() if (row_begin is None and row_end is None and col is None and track is None
-                              and n_dst == plan.n_dst) else None
+    if row_order is not None:
+        a.row_order = row_order.data_ptr()
     if hub is not None:
         hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
-        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=x.device)
+        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=chunk_begin.device)
         a.hub_threshold = plan.hub_threshold
         a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
         a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
         a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
         a.hub_scratch = scratch.data_ptr()
-    a.wide_blocks = wide_blocks_hint(explicit_spans=row_begin is not None or row_end is not None or col is not None,
-                                     has_hub_lists=hub is not None, ldx=ldx, num_edges=plan.num_edges, n_rows=n_dst)
+    if hub_order_slot is not None:
+        a.hub_order_slot = hub_order_slot.data_ptr()
+    return a, (add_x, scratch)
+
+
+def _attach_split_rows(a, split, plan, col=None):
+    """The split-row layout's members: the tail table, and the per-edge tail when it was built for this plan's own col."""
+    a.x_tail, a.ld_tail, a.f_main = split.tail.data_ptr(), int(split.tail.shape[1]), int(split.main.shape[1])
+    if split.edge_tail is not None and split.edge_plan is plan and col is None:
+        a.edge_tail, a.ld_edge_tail = split.edge_tail.data_ptr(), int(split.edge_tail.shape[1])
+
+
+def _describe(entry, what, a, *dtypes):
+    """The kernel symbol a *_describe entry of the library names for `a` (160 bytes hold the longest instantiation)."""
+    buf = ctypes.create_string_buffer(160)
+    L.check(entry(ctypes.byref(a), *dtypes, buf, 160), what)
+    return buf.value.decode()
+
+
+def segment_reduce(plan, x, op, w_csr=None, out=None, act=L.ACT_NONE, self_coef=None, bias=None, add_x=None,
+                   accumulate=False, mean_count=None, row_begin=None, row_end=None, rp_stride=1, col=None,
+                   n_dst=None, describe=False, track=None, track_row_begin=None, wide_blocks=None, out_dtype=None):
+    """One launch of the segment-reduce kernel on `plan` (or on explicit row_begin/row_end/col views of it).  `x` is the table:
+      * a dense float32 [n_src, F] tensor — tfgx_segment_reduce_f32; a table this plan keeps meeting unchanged is served from
+        its promoted layout (verified_layout), a power-of-two row stride may be re-laid (relaid_for_gather);
+      * a SplitRows (the static feature layout) — the same entry on main / tail / per-edge tail;
+      * a HalfRows (a 16-bit table) — tfgx_segment_reduce_h16: float32 arithmetic, the float32 route's bits.  The float32
+        layouts above are not consulted, `track` is refused, and out_dtype = torch.bfloat16 / torch.float16 returns the
+        result as a HalfRows (rounded as the last step; `out` is then a HalfRows too).
+    describe=True launches nothing and returns the kernel symbol the dispatcher picks for these arguments
+    (tfgx_segment_reduce_describe / _h16_describe).  `track` (TFGX_MAX, training forward): int32 [n_dst, F] that receives tie
+    count << 16 | row-relative position of the first maximal edge (tfgx_reduce_args.track; see can_track); with
+    accumulate=True the launch merges into the (out, track) earlier launches stored for earlier sub-spans of the same rows
+    (track_row_begin: the first position of the whole row)."""
+    half = x if isinstance(x, HalfRows) else None
+    if half is not None:
+        if track is not None or track_row_begin is not None:
+            raise L.TfgxError("tfgx_segment_reduce_h16: track: not supported on a 16-bit table (max aggregation is inference-only)")
+    elif out_dtype not in (None, torch.float32):
+        raise TypeError("segment_reduce: out_dtype needs a HalfRows input")
+    lib = L.require_gpu()
+    own_rows = row_begin is None and row_end is None and col is None
+    n_dst = plan.n_dst if n_dst is None else int(n_dst)
+    split = x if isinstance(x, SplitRows) else None
+    verified = None
+    if half is not None:
+        # verified_layout, SplitRows and relaid_for_gather are layouts of float32 rows: none is consulted for a 16-bit table
+        if out_dtype is not None and out_dtype not in L.H16_DTYPES and out_dtype != torch.float32:
+            raise TypeError("segment_reduce: out_dtype must be None, torch.float32, torch.bfloat16 or torch.float16")
+        x_ptr, ldx, F, device = half.table.data_ptr(), half.ld, half.F, half.device
+    else:
+        if split is None and own_rows and track is None and not accumulate and n_dst == plan.n_dst:
+            verified = verified_layout(plan, x, describe=describe)      # a promoted table: served from its layout, checked
+            if verified is not None:
+                table, split = x, verified.rows
+        if split is not None:
+            x, ldx = L.row_major_2d(split.main)
+            F = split.shape[1]
+        else:
+            x, ldx = L.row_major_2d(x)
+            F = int(x.shape[1])
+            if own_rows:
+                x, ldx = relaid_for_gather(x, ldx, plan.hub_info() is not None, dry_run=describe)
+        x_ptr, device = x.data_ptr(), x.device
+    given = out is not None
+    half_out = out_dtype in L.H16_DTYPES
+    if half_out:
+        if out is None:
+            out = HalfRows.empty(n_dst, F, out_dtype, device)
+        assert isinstance(out, HalfRows) and out.dtype == out_dtype and out.F == F, "out must be a HalfRows of out_dtype"
+        out_ptr, ldo = out.table.data_ptr(), out.ld
+    else:
+        if out is None:
+            out = torch.empty((n_dst, F), dtype=torch.float32, device=device)
+        # a HalfRows caller may have meant a 16-bit `out`: that entry says what it takes; the float32 entry has always asserted
+        if half is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == device
+                                     and out.dim() == 2 and int(out.shape[0]) >= n_dst and int(out.shape[1]) == F):
+            raise TypeError("segment_reduce on a HalfRows: out must be a float32 [n_dst, F] tensor on the table's device "
+                            "(or a HalfRows with out_dtype=)")
+        out2, ldo = L.row_major_2d(out)
+        assert out2 is out, "out must be row-major"
+        out_ptr = out.data_ptr()
+    # Launches over the plan's own rows take its walk order and hub lists.  (A launch over the first rows of a larger plan takes
+    # no hub lists: they name rows of the WHOLE plan, and the finalize pass would write the rows past n_dst; long rows are then
+    # walked inline — same sums.)
+    whole_plan = own_rows and n_dst == plan.n_dst
+    order = None
+    if whole_plan and USE_ROW_ORDER and F <= ROW_ORDER_MAX_F:
+        # skewed plans: degree-ordered walk (the rows sharing a wave have similar lengths).  Same-box A/B on R-MAT graphs:
+        # F = 20: -7 .. -16 %, F = 64: -4 .. -11 % (round 2); round 4, after the hub finalize stopped being a latency chain
+        # (profiles/r04_ab_row_order.jsonl, 2.4 M / 123 M and 2^21 / 61 M edges): F = 100: -10 / -11 %, F = 128: -3 / -5 %,
+        # F = 256: -2 .. +1 % (one row per wave there: nothing to balance) — hence the width limit
+        order = plan.row_order()
+    # (the library refuses `track` together with hub lists — hub rows are chunked and do not track: a tracked launch walks
+    # its long rows inline; on a 16-bit table track was refused above)
+    hub = plan.hub_info() if (whole_plan and track is None) else None
+    a, keep = _reduce_args(plan, x_ptr, ldx, F, op, w_csr, n_dst, row_begin, row_end, rp_stride, col, act, accumulate,
+                           self_coef, bias, add_x, mean_count, order, hub)
+    a.out, a.ldo = out_ptr, ldo
+    if split is not None:
+        _attach_split_rows(a, split, plan, col)
+    if verified is not None:
+        a.verify, a.verify_x, a.ld_verify_x = 1, table.data_ptr(), int(table.stride(0))
+        a.n_verify, a.verify_word = int(table.shape[0]), verified.word.data_ptr()
+    if track is not None:
+        a.track, a.ld_track = track.data_ptr(), int(track.stride(0))
+        if track_row_begin is not None:      # positions relative to the WHOLE row when it is reduced span by span
+            a.track_row_begin = track_row_begin.data_ptr()
     if wide_blocks is not None:          # tests / A-B tools: +1 column blocks wherever the layout allows, -1 one burst per row
         a.wide_blocks = int(wide_blocks)
-    if describe:
-        buf = ctypes.create_string_buffer(160)
-        L.check(lib.tfgx_segment_reduce_describe(ctypes.byref(a), buf, 160), "tfgx_segment_reduce_describe")
-        return buf.value.decode()
-    L.check(lib.tfgx_segment_reduce_f32(ctypes.byref(a), L.stream_ptr()), "tfgx_segment_reduce_f32")
+    elif half is not None:               # two measured policies: see the two functions
+        a.wide_blocks = h16_wide_blocks_hint(not own_rows, hub is not None, plan.num_edges, n_dst)
+    else:
+        a.wide_blocks = wide_blocks_hint(explicit_spans=not own_rows, has_hub_lists=hub is not None, ldx=ldx,
+                                         num_edges=plan.num_edges, n_rows=n_dst)
+    if half is not None:
+        dtypes = (L.H16_DTYPES[half.dtype], L.H16_DTYPES[out_dtype] if half_out else L.DT_F32)
+        if describe:
+            return _describe(lib.tfgx_segment_reduce_h16_describe, "tfgx_segment_reduce_h16_describe", a, *dtypes)
+        L.check(lib.tfgx_segment_reduce_h16(ctypes.byref(a), dtypes[0], dtypes[1], L.stream_ptr()), "tfgx_segment_reduce_h16")
+    else:
+        if describe:
+            return _describe(lib.tfgx_segment_reduce_describe, "tfgx_segment_reduce_describe", a)
+        L.check(lib.tfgx_segment_reduce_f32(ctypes.byref(a), L.stream_ptr()), "tfgx_segment_reduce_f32")
+    del keep                             # enqueued: what the struct named by address may go
     _AGG_LAUNCHES[0] += 1
     if verified is not None:
         verified.seen.copy_(verified.word, non_blocking=True)       # read by a later call (verified_layout)
         VERIFIED_STATS["served"] += 1
-    if given:
+    if given and not half_out:           # a caller's float32 tensor written through its raw pointer (a HalfRows has no counter)
         written_by_kernel(out)
     if track is not None:
         written_by_kernel(track)
@@ -1167,76 +1154,77 @@ def aggregate_gemm_applies(x, kernel, op=L.SUM):
 
 def aggregate_gemm(plan, x, op, kernel, w_csr=None, self_coef=None, bias=None, act=L.ACT_NONE, out=None, agg_out=None,
                    training=False):
-    """act(segment_reduce(plan, x, op, w_csr, self_coef) @ kernel + bias) in ONE launch (tfgx_aggregate_gemm_f32: the
-    aggregate goes registers -> LDS -> MFMA and is never read back from HBM), or None when the fused kernel does not take
-    this call (shape outside tfgx_aggregate_gemm_fits, unaligned rows) — the caller then runs the two launches.
+    """act(segment_reduce(plan, x, op, w_csr, self_coef) @ kernel + bias) in ONE launch (the aggregate goes registers -> LDS ->
+    MFMA and is never read back from HBM), or None when the fused kernel does not take this call — the caller then runs the
+    two launches.  `x` is the table:
+      * a dense float32 tensor or a SplitRows — tfgx_aggregate_gemm_f32; declined outside tfgx_aggregate_gemm_fits, on
+        unaligned rows, and at F >= 128 on a large dense table (the rule below);
+      * a HalfRows (a 16-bit table) — tfgx_aggregate_gemm_h16 (include/tfgx_fused_h16.h): float32 arithmetic, float32 C and
+        side output, the bits of this call on x.float() with the same plan; declined outside tfgx_aggregate_gemm_fits and by
+        the measured inference-only rule of _fused_h16_declines (never for a training forward: training=True — the autograd
+        routes over a HalfRows — or an agg_out).  The split / static layouts and relaid_for_gather do not apply to it.
+    Every launch takes the plan's hub lists, walk order and hub_order_slot, at every width.
     agg_out: optional dense [n_dst, F] tensor that ALSO receives the aggregate itself (the training forward: the weight
-    gradient needs it).
-    x may be a HalfRows (a 16-bit table): the launch is tfgx_aggregate_gemm_h16 — float32 arithmetic, float32 C and side output,
-    the bits of this call on x.float() with the same plan.  training=True (the autograd routes over a HalfRows): the measured
-    inference-only declining rule of _fused_h16_declines is not applied."""
+    gradient needs it)."""
     if not FUSE_AGGREGATE_GEMM or op not in (L.SUM, L.MEAN):
         return None
-    if isinstance(x, HalfRows):
-        return _aggregate_gemm_h16(plan, x, op, kernel, w_csr, self_coef, bias, act, out, agg_out, training)
     lib = L.require_gpu()
+    half = x if isinstance(x, HalfRows) else None
     split = x if isinstance(x, SplitRows) else None       # static feature layout: main / tail / per-edge tail (as segment_reduce)
-    x2, ldx = L.row_major_2d(split.main if split is not None else x)
     k2, ldb = L.row_major_2d(L.as_f32(kernel))
-    F, N = (split.shape[1] if split is not None else int(x2.shape[1])), int(k2.shape[1])
-    if int(k2.shape[0]) != F or not lib.tfgx_aggregate_gemm_fits(F, N) or ldx % 4 != 0 or x2.data_ptr() % 16 != 0:
-        return None
+    N = int(k2.shape[1])
+    if half is not None:
+        x_ptr, ldx, F, device = half.table.data_ptr(), half.ld, half.F, half.device      # (a HalfRows keeps its rows 16-byte aligned)
+        if int(k2.shape[0]) != F or not lib.tfgx_aggregate_gemm_fits(F, N):
+            return None
+        if _fused_h16_declines(plan, half, training or agg_out is not None):
+            return None
+    else:
+        x2, ldx = L.row_major_2d(split.main if split is not None else x)
+        F = split.shape[1] if split is not None else int(x2.shape[1])
+        if int(k2.shape[0]) != F or not lib.tfgx_aggregate_gemm_fits(F, N) or ldx % 4 != 0 or x2.data_ptr() % 16 != 0:
+            return None
     hub = plan.hub_info()      # long rows: chunk partials by a launch of the ordinary kernel, folded by the row's lane group
     order = plan.row_order()   # skewed plans: tiles of similar-length rows (degree order), results unchanged
-    if (split is None and agg_out is None and hub is None and F >= 128 and F % 32 == 0 and ldx % 32 == 0 and x2.data_ptr() % 128 == 0
-            and plan.num_edges >= 32 * max(plan.n_dst, 1) and 4 * int(x2.shape[0]) * F > (512 << 20) and not TFGX_FUSE_WIDE):
-        # round 5: at F = 128 the stand-alone aggregation gathers in column blocks (10.2 -> 9.2 ms at products shape), which this
-        # launch's producers do not; on a large dense table the two launches are now ahead at inference — same-box A/B
-        # (profiles/r05_ab_fused_layer_F128.json): GCN layer 128 -> 256 11.05 fused vs 10.53, mean GraphSAGE 10.86 vs 10.40.
-        # The TRAINING forward keeps the fused launch (its side output saves the aggregate's read-back: 14.66 vs 15.14), and so
-        # do small graphs (arxiv shape: the table is cache-resident, 0.238 vs 0.259 ms).
-        return None
-    if split is None:
-        x2, ldx = relaid_for_gather(x2, ldx, hub is not None)      # F = 128 at a 512-byte row stride on a power-law plan
+    if half is None:
+        if (split is None and agg_out is None and hub is None and F >= 128 and F % 32 == 0 and ldx % 32 == 0 and x2.data_ptr() % 128 == 0
+                and plan.num_edges >= 32 * max(plan.n_dst, 1) and 4 * int(x2.shape[0]) * F > (512 << 20) and not TFGX_FUSE_WIDE):
+            # round 5: at F = 128 the stand-alone aggregation gathers in column blocks (10.2 -> 9.2 ms at products shape), which this
+            # launch's producers do not; on a large dense table the two launches are now ahead at inference — same-box A/B
+            # (profiles/r05_ab_fused_layer_F128.json): GCN layer 128 -> 256 11.05 fused vs 10.53, mean GraphSAGE 10.86 vs 10.40.
+            # The TRAINING forward keeps the fused launch (its side output saves the aggregate's read-back: 14.66 vs 15.14), and so
+            # do small graphs (arxiv shape: the table is cache-resident, 0.238 vs 0.259 ms).  The rule does not carry over to a
+            # 16-bit table: see _fused_h16_declines.
+            return None
+        if split is None:
+            x2, ldx = relaid_for_gather(x2, ldx, hub is not None)      # F = 128 at a 512-byte row stride on a power-law plan
+        x_ptr, device = x2.data_ptr(), x2.device
     n_dst = plan.n_dst
     given = out is not None
     if out is None:
-        out = torch.empty((n_dst, N), dtype=torch.float32, device=x2.device)
+        out = torch.empty((n_dst, N), dtype=torch.float32, device=device)
     _, ldc = L.row_major_2d(out)
-    a = L.ReduceArgs()
-    a.row_begin, a.row_end, a.rp_stride = plan.row_ptr.data_ptr(), plan.row_ptr[1:].data_ptr(), 1
-    a.col = plan.col.data_ptr()
-    a.w = 0 if w_csr is None else w_csr.data_ptr()
-    a.n_dst, a.x, a.ldx, a.F = n_dst, x2.data_ptr(), ldx, F
-    a.op = op
-    a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
+    a, keep = _reduce_args(plan, x_ptr, ldx, F, op, w_csr, self_coef=self_coef, row_order=order, hub=hub,
+                           hub_order_slot=plan.hub_order_slot() if hub is not None else None)
     if split is not None:
-        a.x_tail, a.ld_tail, a.f_main = split.tail.data_ptr(), int(split.tail.shape[1]), int(split.main.shape[1])
-        if split.edge_tail is not None and split.edge_plan is plan:
-            a.edge_tail, a.ld_edge_tail = split.edge_tail.data_ptr(), int(split.edge_tail.shape[1])
-    if order is not None:
-        a.row_order = order.data_ptr()
-    if hub is not None:
-        hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
-        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=x2.device)
-        a.hub_threshold = plan.hub_threshold
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
-        a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
-        a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
-        a.hub_scratch = scratch.data_ptr()
-        slot = plan.hub_order_slot()
-        if slot is not None:
-            a.hub_order_slot = slot.data_ptr()
+        _attach_split_rows(a, split, plan)
     if agg_out is not None:
         ao, ldo = L.row_major_2d(agg_out)
         assert ao is agg_out and tuple(agg_out.shape) == (n_dst, F) and ldo % 4 == 0 and agg_out.data_ptr() % 16 == 0
         a.out, a.ldo = agg_out.data_ptr(), ldo
         FUSED_STATS["with_side_output"] += 1
     FUSED_STATS["launches"] += 1
+    if half is not None:
+        FUSED_H16_STATS["launches"] += 1
     _AGG_LAUNCHES[0] += 1
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
-    L.check(lib.tfgx_aggregate_gemm_f32(ctypes.byref(a), L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out), ldc, N,
-                                        L.stream_ptr()), "tfgx_aggregate_gemm_f32")
+    if half is not None:
+        L.check(lib.tfgx_aggregate_gemm_h16(ctypes.byref(a), L.H16_DTYPES[half.dtype], L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out),
+                                            ldc, N, L.stream_ptr()), "tfgx_aggregate_gemm_h16")
+    else:
+        L.check(lib.tfgx_aggregate_gemm_f32(ctypes.byref(a), L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out), ldc, N,
+                                            L.stream_ptr()), "tfgx_aggregate_gemm_f32")
+    del keep                             # enqueued: what the struct named by address may go
     if given:
         written_by_kernel(out)
     written_by_kernel(agg_out)
@@ -1261,62 +1249,6 @@ def _fused_h16_declines(plan, h, training):
     against the float32 column-block gather; at F = 128 on the uniform graph this launch is ahead (6.09 vs 5.50)."""
     return bool(FUSED_H16_DECLINE_HUB_INFERENCE and not training and plan.hub_info() is not None
                 and 2 * h.shape[0] * h.ld > (256 << 20))
-
-
-def _aggregate_gemm_h16(plan, h, op, kernel, w_csr, self_coef, bias, act, out, agg_out, training=False):
-    """aggregate_gemm on a HalfRows: one launch of tfgx_aggregate_gemm_h16 (include/tfgx_fused_h16.h), or None when the shape
-    is outside tfgx_aggregate_gemm_fits or the measured rule of _fused_h16_declines says so (never for a training forward:
-    training=True, or an agg_out).  Hub lists, the walk order and hub_order_slot come from the plan exactly as for
-    float32; the split / static layouts and relaid_for_gather do not apply to a 16-bit table."""
-    lib = L.require_gpu()
-    k2, ldb = L.row_major_2d(L.as_f32(kernel))
-    F, N = h.F, int(k2.shape[1])
-    if int(k2.shape[0]) != F or not lib.tfgx_aggregate_gemm_fits(F, N):
-        return None
-    if _fused_h16_declines(plan, h, training or agg_out is not None):
-        return None
-    hub = plan.hub_info()
-    order = plan.row_order()
-    n_dst = plan.n_dst
-    given = out is not None
-    if out is None:
-        out = torch.empty((n_dst, N), dtype=torch.float32, device=h.device)
-    _, ldc = L.row_major_2d(out)
-    a = L.ReduceArgs()
-    a.row_begin, a.row_end, a.rp_stride = plan.row_ptr.data_ptr(), plan.row_ptr[1:].data_ptr(), 1
-    a.col = plan.col.data_ptr()
-    a.w = 0 if w_csr is None else w_csr.data_ptr()
-    a.n_dst, a.x, a.ldx, a.F = n_dst, h.table.data_ptr(), h.ld, F
-    a.op = op
-    a.self_coef = 0 if self_coef is None else self_coef.data_ptr()
-    if order is not None:
-        a.row_order = order.data_ptr()
-    if hub is not None:
-        hub_rows, chunk_ptr, chunk_begin, chunk_end, _ = hub
-        scratch = torch.empty((int(chunk_begin.shape[0]), F), dtype=torch.float32, device=h.device)
-        a.hub_threshold = plan.hub_threshold
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), chunk_ptr.data_ptr()
-        a.hub_chunk_begin, a.hub_chunk_end = chunk_begin.data_ptr(), chunk_end.data_ptr()
-        a.n_hub_rows, a.n_hub_chunks = int(hub_rows.shape[0]), int(chunk_begin.shape[0])
-        a.hub_scratch = scratch.data_ptr()
-        slot = plan.hub_order_slot()
-        if slot is not None:
-            a.hub_order_slot = slot.data_ptr()
-    if agg_out is not None:
-        ao, ldo = L.row_major_2d(agg_out)
-        assert ao is agg_out and tuple(agg_out.shape) == (n_dst, F) and ldo % 4 == 0 and agg_out.data_ptr() % 16 == 0
-        a.out, a.ldo = agg_out.data_ptr(), ldo
-        FUSED_STATS["with_side_output"] += 1
-    FUSED_STATS["launches"] += 1
-    FUSED_H16_STATS["launches"] += 1
-    _AGG_LAUNCHES[0] += 1
-    bias_t = None if bias is None else L.as_f32(bias).contiguous()
-    L.check(lib.tfgx_aggregate_gemm_h16(ctypes.byref(a), L.H16_DTYPES[h.dtype], L.ptr(k2), ldb, L.ptr(bias_t), act, L.ptr(out),
-                                        ldc, N, L.stream_ptr()), "tfgx_aggregate_gemm_h16")
-    if given:
-        written_by_kernel(out)
-    written_by_kernel(agg_out)
-    return out
 
 
 def can_track(plan, x2, ldx):
