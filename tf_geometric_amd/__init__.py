@@ -21,11 +21,20 @@ from . import utils
 from .graph_capture import CapturedForward, CapturedTrainStep
 
 
-def prepare_half_features(x, dtype=_torch.bfloat16):
+def prepare_half_features(x, dtype=_torch.bfloat16, gemm_operand=False, ld=None):
     """Store a float32 feature table in 16 bits (torch.bfloat16 by default, or torch.float16) for the aggregation kernels:
-    a HalfRows on the line-friendly row stride, quantised by tfgx_rows_f32_to_h16 (round to nearest even).  Arithmetic stays
-    float32; the result of every reduce over it equals the float32 route's on half_features_to_f32(h) bit for bit."""
-    return HalfRows.from_dense(x, dtype=dtype)
+    a HalfRows on the line-friendly row stride (or on `ld` elements), quantised by tfgx_rows_f32_to_h16 (round to nearest
+    even).  Arithmetic stays float32; the result of every reduce over it equals the float32 route's on
+    half_features_to_f32(h) bit for bit.
+
+    gemm_operand=True also declares the table for the GEMM position: GCN with units <= num_features, GAT and the mean / sum
+    GraphSAGE layers then read it in their projections and weight gradients (include/tfgx_gemm_h16.h) — the float32 layer's
+    bits on half_features_to_f32(h), outputs and parameter gradients, with no widened [N, F] copy.  The flag is the caller's
+    choice and nothing falls back to a widened copy behind it.  Measured (tools/bench_gemm_half.py): on no
+    shape is reading the table behind widening it first (1.25x to 7x ahead); against a float32 copy that is already held, the
+    narrow-output (skinny) route is 34-38 % faster, the row kernel level, and the LDS-staged kernel slower — 233 k x 602 -> 64
+    by 22 %, -> 256 by 7 %."""
+    return HalfRows.from_dense(x, dtype=dtype, ld=ld, gemm_operand=gemm_operand)
 
 
 def half_features_to_f32(h):

@@ -11,7 +11,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libtfgx.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
-SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_misc.hip", "tfgx_backward.hip",
+SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
            "tfgx_normgrad.hip"]
@@ -31,7 +31,10 @@ def build(force=False, verbose=True):
     fused_h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_fused_h16.h")
     # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
     fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
+    gemm_hdrs = [os.path.join(CSRC, "tfgx_gemm_kernels.h"), os.path.join(CSRC, "tfgx_mfma.h")]      # the GEMM templates both GEMM sources instantiate
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
+                "tfgx_gemm.hip": gemm_hdrs,
+                "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
                 "tfgx_fused.hip": fused_hdrs,
                 "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr] + fused_hdrs,
                 "tfgx_dropedge.hip": [os.path.join(_HERE, "..", "include", "tfgx_dropedge.h")],

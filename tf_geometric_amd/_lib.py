@@ -266,6 +266,18 @@ FUSED_H16_SIGNATURES = {
     "tfgx_aggregate_gemm_h16_describe": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I64, ctypes.c_char_p, ctypes.c_size_t]),
 }
 
+# include/tfgx_gemm_h16.h (the dense GEMM and its weight gradient reading a 16-bit table): its own header, version and table —
+# checked against that header by tests/test_gemm_h16_abi.py.
+GEMM_H16_ABI_VERSION = 1
+GEMM_H16_SIGNATURES = {
+    "tfgx_gemm_h16_version": (ctypes.c_int, []),
+    "tfgx_gemm_bias_act_cols_ws_h16": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _P, _I32, _I64, _P, _I64, _I64, _I64, _I64, _P, _SZ,
+                                                      _P]),
+    "tfgx_gemm_h16_describe": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _P, _I32, _I64, _P, _I64, _I64, _I64, _I64, _P, _SZ,
+                                              ctypes.c_char_p, ctypes.c_size_t]),
+    "tfgx_gemm_tn_gated_h16": (ctypes.c_int, [_P, _I32, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
+}
+
 
 
 class DropEdgePlan(ctypes.Structure):
@@ -401,6 +413,10 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in GEMM_H16_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     for name, (res, args) in DROPEDGE_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -457,6 +473,10 @@ def load_library():
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_dropedge ABI {} but this package binds {} "
                         "(include/tfgx_dropedge.h): rebuild with __graft_entry__.build()".format(
                             LIB_PATH, lib.tfgx_dropedge_version(), DROPEDGE_ABI_VERSION))
+    if lib.tfgx_gemm_h16_version() != GEMM_H16_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_gemm_h16 ABI {} but this package binds {} "
+                        "(include/tfgx_gemm_h16.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_gemm_h16_version(), GEMM_H16_ABI_VERSION))
     if lib.tfgx_fused_h16_version() != FUSED_H16_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_fused_h16 ABI {} but this package binds {} "
                         "(include/tfgx_fused_h16.h): rebuild with __graft_entry__.build()".format(

@@ -263,54 +263,61 @@ class _SageWide(torch.autograd.Function):
     (tfgx_aggregate_gemm_f32 / _h16 straight into its half of h, aggregate written beside it for d/dkn), the self half the GEMM."""
 
     @staticmethod
-    def forward(ctx, plan, mean, x, xs, ks, kn, w_csr, bias, act, table=None):
+    def forward(ctx, plan, mean, x, xs, ks, kn, w_csr, bias, act, table=None, self_table=None):
         """x, `table`: as in _Aggregate.forward.  xs: what the self half reads — x itself, or over a HalfRows the widened
-        table (widen), whose gradient reaches the same sink: the two halves' d/dx are summed by autograd either way."""
-        n, F, na, nb = int(xs.shape[0]), int(kn.shape[0]), int(ks.shape[1]), int(kn.shape[1])
-        h = torch.empty((n, na + nb), dtype=torch.float32, device=xs.device)
+        table (widen), whose gradient reaches the same sink: the two halves' d/dx are summed by autograd either way.
+        `self_table`: a HalfRows declared a GEMM operand, which the self half reads in place of a widened copy (xs is then its
+        gradient sink, like x)."""
+        xr = _rows_of(xs, self_table)
+        n, F, na, nb = int(xr.shape[0]), int(kn.shape[0]), int(ks.shape[1]), int(kn.shape[1])
+        h = torch.empty((n, na + nb), dtype=torch.float32, device=kn.device)
         bd = None if bias is None else bias.detach().contiguous()
-        agg = torch.empty((n, F), dtype=torch.float32, device=xs.device) if ctx.needs_input_grad[5] else None
+        agg = torch.empty((n, F), dtype=torch.float32, device=kn.device) if ctx.needs_input_grad[5] else None
         got = aggregate_gemm(plan, x.detach() if table is None else table, L.MEAN if mean else L.SUM, kn.detach(),
                              w_csr=None if w_csr is None else w_csr.detach(),
                              bias=None if bd is None else bd[na:].contiguous(), act=act, out=h[:, na:], agg_out=agg, training=True)
         if got is None:
             raise L.TfgxError("_SageWide: the fused launch declined (ask plan.aggregate_gemm_applies first)")
-        gemm_bias_act(xs.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
-        ctx.plan, ctx.mean, ctx.act, ctx.na, ctx.table = plan, mean, act, na, table
+        gemm_bias_act(xr, ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
+        ctx.plan, ctx.mean, ctx.act, ctx.na, ctx.table, ctx.self_table = plan, mean, act, na, table, self_table
         ctx.save_for_backward(xs, ks, kn, w_csr, bias, agg, h if act == L.ACT_RELU else None)
         return h
 
     @staticmethod
     def backward(ctx, g):
         xs, ks, kn, w_csr, bias, agg, h = ctx.saved_tensors
-        _, _, need_x, need_xs, need_ks, _, _, need_b, _, _ = ctx.needs_input_grad
+        _, _, need_x, need_xs, need_ks, _, _, need_b, _, _, _ = ctx.needs_input_grad
         na, upstream, want_b = ctx.na, need_x or need_xs, bias is not None and need_b
         g, gate = _behind_relu(g, h, ctx.act, agg, upstream)          # gated: layer 0, x carries no gradient
         gs, gn = g[:, :na], g[:, na:]
-        gxs, gks, gba = _linear_grads(xs, ks, gs, upstream, need_ks, want_b, gate=None if gate is None else gate[:, :na])
+        gxs, gks, gba = _linear_grads(ctx.self_table if ctx.self_table is not None else xs, ks, gs, upstream, need_ks, want_b,
+                                      gate=None if gate is None else gate[:, :na])
         gkn, gbb = _projection_grads(agg, gn, want_b, None if gate is None else gate[:, na:])
         gx = None
         if upstream:
             gx, _, _ = _source_grads(ctx.plan, ctx.mean, None, ctx.table, w_csr, None, gn, True, False, False, kn)
         gb = torch.cat([gba, gbb]) if want_b else None
-        return None, None, gx if need_x else None, gxs if need_xs else None, gks, gkn, None, gb, None, None
+        return None, None, gx if need_x else None, gxs if need_xs else None, gks, gkn, None, gb, None, None, None
 
 
 def sage_wide(plan, op, x, ks, kn, w_csr=None, bias=None, act=L.ACT_NONE, rows=None):
     """Differentiable mean / sum GraphSAGE layer body (concat form, aggregation first) with the neighbour half on the fused
     launch, or None when it does not take the shape.  Edge weights are constants here (trainable ones take the un-fused route).
     rows: x's static layout (plan.static_rows) or None / x itself.
-    x may be a HalfRows (rows is not consulted; the self half reads the widened table; trainable edge weights:
-    NotImplementedError)."""
+    x may be a HalfRows (rows is not consulted; the self half reads the widened table, or the table itself when it was declared
+    a GEMM operand; trainable edge weights: NotImplementedError)."""
     table = x if isinstance(x, HalfRows) else (rows if isinstance(rows, SplitRows) else None)
     if op not in (L.SUM, L.MEAN) or not aggregate_gemm_applies(x if table is None else table, kn, op):
         return None
-    xs = x
+    xs, self_table = x, None
     if table is x:
         x, w_csr = _half_source(table, w_csr)
-        xs = widen(table)
+        if table.gemm_operand:      # the self half reads the table itself; its d/dx reaches the same sink as the aggregation's
+            xs, self_table = x, table
+        else:
+            xs = widen(table)
     return _SageWide.apply(plan, op == L.MEAN, x, xs, L.as_f32(ks), L.as_f32(kn), w_csr,
-                           None if bias is None else L.as_f32(bias), act, table)
+                           None if bias is None else L.as_f32(bias), act, table, self_table)
 
 
 # Gradient of max aggregation (tf.math.unsorted_segment_max, ties share evenly):
@@ -632,6 +639,20 @@ def aggregate(plan, x, op, w_csr=None, self_coef=None, rows=None, bias=None, act
     return _Aggregate.apply(plan, op == L.MEAN, x, w_csr, self_coef, table, bias, act)
 
 
+def _gemm_source(x):
+    """(the tensor in x's autograd position, the table the GEMMs read) of a dense operand.  A float32 tensor: (x, None).  A
+    HalfRows: its float32 gradient sink (_half_grad_proxy; None when the table's source wants no gradient — d/dx is then not
+    computed) and the table itself, which the operators keep on ctx as an attribute: it is no tensor to save_for_backward."""
+    if isinstance(x, HalfRows):
+        return _half_grad_proxy(x), x
+    return x, None
+
+
+def _rows_of(x, table):
+    """What the kernels read: the table when there is one, else the detached tensor."""
+    return table if table is not None else x.detach()
+
+
 def _linear_grads(x, kernel, g, need_x, need_k, need_b, gate=None):
     """(d/dx, d/dkernel, d/dbias) of x @ kernel + bias given g (which may be a column slice of a wider gradient).
     `gate`: the layer's ReLU output when g is still UN-masked — only valid without d/dx (the reduction kernel applies
@@ -642,7 +663,7 @@ def _linear_grads(x, kernel, g, need_x, need_k, need_b, gate=None):
     # d/dkernel = x^T @ g and d/dbias = column sums of g: ONE reduction over the node dimension (tfgx_gemm_tn_f32)
     gk = gb = None
     if need_k or need_b:
-        gk, gb = gemm_tn(x.detach(), g, want_bias=need_b, gate=gate)
+        gk, gb = gemm_tn(x if isinstance(x, HalfRows) else x.detach(), g, want_bias=need_b, gate=gate)
         if not need_k:
             gk = None
     return gx, gk, gb
@@ -654,13 +675,15 @@ class _DualLinear(torch.autograd.Function):
     no bias add, no activation pass; the backward slices the (masked) gradient by column views."""
 
     @staticmethod
-    def forward(ctx, x, ka, r, kb, bias, act):
-        n, na, nb = int(x.shape[0]), int(ka.shape[1]), int(kb.shape[1])
-        h = torch.empty((n, na + nb), dtype=torch.float32, device=x.device)
+    def forward(ctx, x, ka, r, kb, bias, act, table=None):
+        """x, `table`: _gemm_source of the self operand (a HalfRows: the GEMM and the weight gradient read the table)."""
+        xr = _rows_of(x, table)
+        n, na, nb = int(xr.shape[0]), int(ka.shape[1]), int(kb.shape[1])
+        h = torch.empty((n, na + nb), dtype=torch.float32, device=ka.device)
         bd = None if bias is None else bias.detach().contiguous()
-        gemm_bias_act(x.detach(), ka.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
+        gemm_bias_act(xr, ka.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
         gemm_bias_act(r.detach(), kb.detach(), bias=None if bd is None else bd[na:], act=act, out=h[:, na:])
-        ctx.act, ctx.na = act, na
+        ctx.act, ctx.na, ctx.table = act, na, table
         ctx.save_for_backward(x, ka, r, kb, bias, h if act == L.ACT_RELU else None)
         return h
 
@@ -674,10 +697,11 @@ class _DualLinear(torch.autograd.Function):
         gated = relu and not need[0] and not need[2] and GATED_WEIGHT_GRADIENTS
         g = relu_backward(g, h) if (relu and not gated) else g.contiguous()
         want_b = bias is not None and need[4]
-        gx, gka, gba = _linear_grads(x, ka, g[:, :na], need[0], need[1], want_b, gate=h[:, :na] if gated else None)
+        gx, gka, gba = _linear_grads(ctx.table if ctx.table is not None else x, ka, g[:, :na], need[0], need[1], want_b,
+                                     gate=h[:, :na] if gated else None)
         gr, gkb, gbb = _linear_grads(r, kb, g[:, na:], need[2], need[3], want_b, gate=h[:, na:] if gated else None)
         gb = torch.cat([gba, gbb]) if want_b else None
-        return gx, gka, gr, gkb, gb, None
+        return gx, gka, gr, gkb, gb, None, None
 
 
 class _SageNarrow(torch.autograd.Function):
@@ -686,15 +710,17 @@ class _SageNarrow(torch.autograd.Function):
     the aggregation's epilogues carry bias + activation, nothing is concatenated."""
 
     @staticmethod
-    def forward(ctx, plan, mean, x, ks, kn, w_csr, bias, act):
-        n, na, nb = int(x.shape[0]), int(ks.shape[1]), int(kn.shape[1])
-        h = torch.empty((n, na + nb), dtype=torch.float32, device=x.device)
+    def forward(ctx, plan, mean, x, ks, kn, w_csr, bias, act, table=None):
+        """x, `table`: _gemm_source of the features (a HalfRows: both projections and the weight gradient read the table)."""
+        xr = _rows_of(x, table)
+        n, na, nb = int(xr.shape[0]), int(ks.shape[1]), int(kn.shape[1])
+        h = torch.empty((n, na + nb), dtype=torch.float32, device=ks.device)
         bd = None if bias is None else bias.detach().contiguous()
-        gemm_bias_act(x.detach(), ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
-        z = gemm_bias_act(x.detach(), kn.detach(), out=gather_friendly_empty(n, nb, x.device))
+        gemm_bias_act(xr, ks.detach(), bias=None if bd is None else bd[:na], act=act, out=h[:, :na])
+        z = gemm_bias_act(xr, kn.detach(), out=gather_friendly_empty(n, nb, ks.device))
         segment_reduce(plan, z, L.MEAN if mean else L.SUM, w_csr=None if w_csr is None else w_csr.detach(),
                        out=h[:, na:], act=act, bias=None if bd is None else bd[na:].contiguous())
-        ctx.plan, ctx.mean, ctx.act, ctx.na = plan, mean, act, na
+        ctx.plan, ctx.mean, ctx.act, ctx.na, ctx.table = plan, mean, act, na, table
         ctx.save_for_backward(x, ks, kn, w_csr, bias, h if act == L.ACT_RELU else None)
         return h
 
@@ -723,33 +749,38 @@ class _SageNarrow(torch.autograd.Function):
         segment_reduce(pt, gn, L.SUM, w_csr=_transposed_weights(plan, w_csr, t2d), out=D[:, na:])
         gks = gkn = gb = gx = None
         if need[3] or need[4] or want_b:
-            gW, gb_all = gemm_tn(x.detach(), D, want_bias=want_b)
+            gW, gb_all = gemm_tn(_rows_of(x, ctx.table), D, want_bias=want_b)
             gks, gkn = (gW[:, :na] if need[3] else None), (gW[:, na:] if need[4] else None)
             if want_b:
                 gb = torch.cat([gb_all[:na], gbb])
         if need[2]:
             gx = gemm_bias_act(D, transpose(torch.cat([ks.detach(), kn.detach()], dim=1)))
-        return None, None, gx, gks, gkn, None, gb, None
+        return None, None, gx, gks, gkn, None, gb, None, None
 
 
 def sage_narrow(plan, op, x, ks, kn, w_csr=None, bias=None, act=L.ACT_NONE):
     """Fused differentiable mean / sum GraphSAGE layer body (concat form, neighbour projection first).  The edge weights
     are treated as constants (callers route trainable edge weights through the un-fused operators)."""
+    x, table = _gemm_source(x)
     return _SageNarrow.apply(plan, op == L.MEAN, x, L.as_f32(ks), L.as_f32(kn), w_csr,
-                             None if bias is None else L.as_f32(bias), act)
+                             None if bias is None else L.as_f32(bias), act, table)
 
 
 def dual_linear(x, ka, r, kb, bias=None, act=L.ACT_NONE):
-    return _DualLinear.apply(x, L.as_f32(ka), r, L.as_f32(kb), None if bias is None else L.as_f32(bias), act)
+    """x (the self operand) may be a HalfRows."""
+    x, table = _gemm_source(x)
+    return _DualLinear.apply(x, L.as_f32(ka), r, L.as_f32(kb), None if bias is None else L.as_f32(bias), act, table)
 
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, kernel, bias, act, gathered=False):
-        """gathered=True: the rows are gathered by an aggregation next — written at a line-friendly stride."""
-        dst = gather_friendly_empty(int(x.shape[0]), int(kernel.shape[1]), x.device) if gathered else None
-        out = gemm_bias_act(x.detach(), kernel.detach(), bias=None if bias is None else bias.detach(), act=act, out=dst)
-        ctx.act = act
+    def forward(ctx, x, kernel, bias, act, gathered=False, table=None):
+        """gathered=True: the rows are gathered by an aggregation next — written at a line-friendly stride.
+        x, `table`: _gemm_source of the operand (a HalfRows: the GEMM and the weight gradient read the table)."""
+        xr = _rows_of(x, table)
+        dst = gather_friendly_empty(int(xr.shape[0]), int(kernel.shape[1]), kernel.device) if gathered else None
+        out = gemm_bias_act(xr, kernel.detach(), bias=None if bias is None else bias.detach(), act=act, out=dst)
+        ctx.act, ctx.table = act, table
         ctx.save_for_backward(x, kernel, bias, out)
         return out
 
@@ -759,15 +790,17 @@ class _Linear(torch.autograd.Function):
         relu = ctx.act == L.ACT_RELU
         gated = relu and not ctx.needs_input_grad[0] and GATED_WEIGHT_GRADIENTS      # no d/dx: mask applied inside the reduction kernel
         g = relu_backward(g, out) if (relu and not gated) else g.contiguous()
-        gx, gk, gb = _linear_grads(x, kernel, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                   bias is not None and ctx.needs_input_grad[2], gate=out if gated else None)
-        return gx, gk, gb, None, None
+        gx, gk, gb = _linear_grads(ctx.table if ctx.table is not None else x, kernel, g, ctx.needs_input_grad[0],
+                                   ctx.needs_input_grad[1], bias is not None and ctx.needs_input_grad[2], gate=out if gated else None)
+        return gx, gk, gb, None, None, None
 
 
 def linear(x, kernel, bias=None, act=L.ACT_NONE, gathered=False):
     """act(x @ kernel + bias): forward on the MFMA kernel, differentiable.  gathered=True when an aggregation reads the
-    result next (plan.gather_friendly_ld)."""
-    return _Linear.apply(x, L.as_f32(kernel), None if bias is None else L.as_f32(bias), act, gathered)
+    result next (plan.gather_friendly_ld).  x may be a HalfRows: the forward and the weight gradient read the table
+    (tfgx_gemm_bias_act_cols_ws_h16 / tfgx_gemm_tn_gated_h16); d/dx is computed only when the table's source requires grad."""
+    x, table = _gemm_source(x)
+    return _Linear.apply(x, L.as_f32(kernel), None if bias is None else L.as_f32(bias), act, gathered, table)
 
 
 class _ProjectQKV(torch.autograd.Function):
@@ -778,26 +811,28 @@ class _ProjectQKV(torch.autograd.Function):
     Three separate linear layers read the 561 MB Reddit-shaped x six times per training step; this reads it three times."""
 
     @staticmethod
-    def forward(ctx, x, wq, bq, wk, bk, wv, act):
-        n, A, U = int(x.shape[0]), int(wq.shape[1]), int(wv.shape[1])
-        xd = x.detach()
+    def forward(ctx, x, wq, bq, wk, bk, wv, act, table=None):
+        """x, `table`: _gemm_source of the features (a HalfRows: the projections and the weight gradient read the table)."""
+        xd = _rows_of(x, table)
+        n, A, U = int(xd.shape[0]), int(wq.shape[1]), int(wv.shape[1])
         w_qk = torch.cat([wq.detach(), wk.detach()], dim=1).contiguous()
         b_qk = None if bq is None else torch.cat([bq.detach().reshape(-1), bk.detach().reshape(-1)])
         qk = gemm_bias_act(xd, w_qk, bias=b_qk, act=act)
-        V = gemm_bias_act(xd, wv.detach(), out=gather_friendly_empty(n, U, x.device))
+        V = gemm_bias_act(xd, wv.detach(), out=gather_friendly_empty(n, U, wv.device))
         # K rows narrower than a 128-byte line are gathered per edge: inside [Q | K] a line holds half as many of them
         # (nn/conv/gat._project_qkv); a copy of [n, A] floats costs ~10 us
         K = qk[:, A:].contiguous() if A <= 16 else qk[:, A:]
-        ctx.act, ctx.A = act, A
+        ctx.act, ctx.A, ctx.table = act, A, table
         ctx.save_for_backward(x, wq, wk, wv, bq, qk if act == L.ACT_RELU else None)
         return qk[:, :A], K, V
 
     @staticmethod
     def backward(ctx, gQ, gK, gV):
         x, wq, wk, wv, bq, qk = ctx.saved_tensors
-        A, U, n = ctx.A, int(wv.shape[1]), int(x.shape[0])
+        xd = _rows_of(x, ctx.table)
+        A, U, n = ctx.A, int(wv.shape[1]), int(xd.shape[0])
         need = ctx.needs_input_grad
-        D = torch.empty((n, 2 * A + U), dtype=torch.float32, device=x.device)
+        D = torch.empty((n, 2 * A + U), dtype=torch.float32, device=wv.device)
         if ctx.act == L.ACT_RELU:
             relu_backward(gQ, qk[:, :A], into=D[:, :A])
             relu_backward(gK, qk[:, A:], into=D[:, A:2 * A])
@@ -807,19 +842,20 @@ class _ProjectQKV(torch.autograd.Function):
         D[:, 2 * A:] = gV
         gwq = gwk = gwv = gbq = gbk = gx = None
         if need[1] or need[2] or need[3] or need[4] or need[5]:
-            gW, gb = gemm_tn(x.detach(), D, want_bias=bq is not None and (need[2] or need[4]))
+            gW, gb = gemm_tn(xd, D, want_bias=bq is not None and (need[2] or need[4]))
             gwq, gwk, gwv = gW[:, :A], gW[:, A:2 * A], gW[:, 2 * A:]
             if gb is not None:
                 gbq, gbk = gb[:A], gb[A:2 * A]
         if need[0]:
             gx = gemm_bias_act(D, transpose(torch.cat([wq.detach(), wk.detach(), wv.detach()], dim=1)))
-        return gx, gwq, gbq, gwk, gbk, gwv, None
+        return gx, gwq, gbq, gwk, gbk, gwv, None, None
 
 
 def project_qkv(x, wq, bq, wk, bk, wv, act):
     """Differentiable (Q, K, V) of a GAT layer on dense features; Q and K share the (fused-code) activation `act`."""
     f = L.as_f32
-    return _ProjectQKV.apply(x, f(wq), None if bq is None else f(bq), f(wk), None if bk is None else f(bk), f(wv), act)
+    x, table = _gemm_source(x)
+    return _ProjectQKV.apply(x, f(wq), None if bq is None else f(bq), f(wk), None if bk is None else f(bk), f(wv), act, table)
 
 
 class _GatAttention(torch.autograd.Function):

@@ -348,7 +348,8 @@ def gat(x, edge_index,
     """
     Functional GAT (reference: gat.py:13-122; same arguments, plus an optional `cache` dict for the CSR plan).
 
-    :param x: [num_nodes, num_features]
+    :param x: [num_nodes, num_features]; dense, sparse, or a plan.HalfRows (16-bit table) declared a GEMM operand
+        (gemm_operand=True): the projections read the table itself, the bits of the float32 layer on x.float()
     :param edge_index: [2, num_edges]
     :param split_value_heads: True -> V is split into heads and the heads are concatenated (:112);
         False -> kernel is [F, units*num_heads] and the heads are averaged (:114).
@@ -356,7 +357,8 @@ def gat(x, edge_index,
     """
     lib = L.require_gpu()
     from ...plan import HalfRows
-    if isinstance(x, HalfRows):
+    half = isinstance(x, HalfRows)
+    if half and not x.gemm_operand:
         raise TypeError("gat multiplies x by its query / key / value kernels before aggregating: a HalfRows (16-bit table) is "
                         "taken by the aggregation kernels only — 16-bit GEMM operands are out of scope; pass x.float()")
     drop = float(edge_drop_rate) if training else 0.0           # SparseMatrix.dropout(rate, training) (:85)
@@ -386,7 +388,7 @@ def gat(x, edge_index,
         h = h[:, :U_out].contiguous()
         return act_post(h) if act_post is not None else h
     xs = sparse_features(x)
-    x = xs if xs is not None else L.as_f32(x)
+    x = xs if xs is not None else (x if half else L.as_f32(x))
     n = int(x.shape[0])
     plan = CsrPlan.from_cache(edge_index, n, n, cache)
     if drop > 0.0 or AG.needs_grad(None if xs is not None else x, query_kernel, query_bias, key_kernel, key_bias, kernel,

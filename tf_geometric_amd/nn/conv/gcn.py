@@ -165,7 +165,9 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     Functional GCN (reference: gcn.py:225-290; same arguments).
 
     :param x: [num_nodes, num_features]; dense, or sparse (this package's SparseMatrix / a torch sparse COO tensor), or a
-        plan.HalfRows (16-bit table) when the layer aggregates x itself: kernel is None or units > num_features
+        plan.HalfRows (16-bit table) when the layer aggregates x itself: kernel is None or units > num_features — or at
+        any width when the table was declared a GEMM operand (HalfRows(..., gemm_operand=True)): x @ kernel then reads the
+        table itself (tfgx_gemm_bias_act_cols_ws_h16), the bits of the float32 layer on x.float()
     :param sparse_adj: SparseMatrix adjacency
     :param kernel: [num_features, num_output_features] or None (skip the GEMM, :266-267)
     :param num_or_size_splits: accepted for compatibility; it bounds memory in the reference and never changes
@@ -174,12 +176,13 @@ def gcn(x, sparse_adj, kernel, bias=None, activation=None, norm="both", add_self
     """
     L.require_gpu()
     half = isinstance(x, HalfRows)
-    if half and kernel is not None and not x.F < int(kernel.shape[1]):
+    if half and not x.gemm_operand and kernel is not None and not x.F < int(kernel.shape[1]):
         raise TypeError("gcn multiplies x by its kernel before aggregating when units <= num_features: a HalfRows (16-bit "
                         "table) is taken by the aggregation kernels only (kernel=None, or units > num_features, where the "
                         "layer aggregates x itself) — 16-bit GEMM operands are out of scope; pass x.float()")
-    # a 16-bit table takes the aggregation-first branches below on tfgx_aggregate_gemm_h16 / tfgx_segment_reduce_h16 and is read
-    # as it is: the static layouts (plan.static_rows / static_aggregate: promotion, memo) are not consulted
+    # a 16-bit table takes the aggregation-first branches below on tfgx_aggregate_gemm_h16 / tfgx_segment_reduce_h16 (one
+    # declared a GEMM operand also the GEMM-first ones: gemm_bias_act / AG.linear read it) and is read as it is: the static
+    # layouts (plan.static_rows / static_aggregate: promotion, memo) are not consulted
     layouts = None if half else cache
     xs = None if half else sparse_features(x)
     if xs is not None:

@@ -27,6 +27,12 @@ def _refuse_half(x, who):
                         "aggregation kernels only — 16-bit GEMM operands are out of scope; pass x.float()".format(who))
 
 
+def _gemm_table(x):
+    """Is x a 16-bit table declared for the GEMM position (HalfRows(..., gemm_operand=True))?  The projections then read it as
+    it is (tfgx_gemm_bias_act_cols_ws_h16 / tfgx_gemm_tn_gated_h16) and the layer takes the float32 layer's routes."""
+    return isinstance(x, HalfRows) and x.gemm_operand
+
+
 def _tail(h, post, normalize):
     """The end of a layer at inference: what the activation leaves to a torch op (post), the in-place l2-normalise kernel."""
     if post is not None:
@@ -113,8 +119,8 @@ def _concat_fused(x, plan, w_csr, ws, wn, bias, activation, normalize, op, cache
     if aggregate_gemm(plan, static_rows(x, plan, cache), op, wn, w_csr=w_csr,
                       bias=None if bias_t is None else bias_t[ku_x:].contiguous(), act=act, out=h[:, ku_x:]) is None:
         return None
-    # x.float(): a HalfRows widens here (tfgx_rows_h16_to_f32); a float32 tensor is itself
-    gemm_bias_act(x.float(), ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
+    # x.float(): a HalfRows widens here (tfgx_rows_h16_to_f32) unless it was declared a GEMM operand; a float32 tensor is itself
+    gemm_bias_act(x if _gemm_table(x) else x.float(), ws, bias=None if bias_t is None else bias_t[:ku_x], act=act, out=h[:, :ku_x])
     return _tail(h, post, normalize)
 
 
@@ -137,8 +143,10 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
     epilogue and the result lands directly in its half of the output.  Same value up to fp32 re-association.
     A HalfRows x (16-bit storage): aggregation first with concat takes the fused launch on the 16-bit table
     (tfgx_aggregate_gemm_h16); otherwise the neighbour half aggregates on tfgx_segment_reduce_h16 into float32 and the
-    projections run on the float32 GEMM.  The self half reads x.float()."""
-    if isinstance(x, HalfRows):
+    projections run on the float32 GEMM.  The self half reads x.float().
+    A HalfRows declared a GEMM operand takes the float32 layer's routes instead — the narrow one (GEMM first) included —
+    with every projection reading the table: the float32 layer's bits on x.float(), and no widened copy."""
+    if isinstance(x, HalfRows) and not x.gemm_operand:
         plan, w_csr = _graph(x, edge_index, edge_weight, cache)
         ws, wn = L.as_f32(self_kernel), L.as_f32(neighbor_kernel)
         if not int(wn.shape[1]) < x.F and concat and not AG.needs_grad(edge_weight):
@@ -150,10 +158,22 @@ def _self_neighbor_sage(x, edge_index, edge_weight, self_kernel, neighbor_kernel
                 return h
         reduced = AG.aggregate(plan, x, op, w_csr) if AG.needs_grad(x, edge_weight) else segment_reduce(plan, x, op, w_csr=w_csr)
         return _combine(ws, AG.widen(x), wn, reduced, bias, activation, concat, normalize)
-    x = L.as_f32(x)
+    half = _gemm_table(x)
+    x = x if half else L.as_f32(x)
     wn = L.as_f32(neighbor_kernel)
     ws = L.as_f32(self_kernel)
     F, ku_x, ku_n = int(x.shape[1]), int(ws.shape[1]), int(wn.shape[1])
+    if half and not ku_n < F:
+        # aggregation first over the table (as for any HalfRows above; the static layouts are float32-only), the self half
+        # from the table too
+        plan, w_csr = _graph(x, edge_index, edge_weight, cache)
+        if concat and not AG.needs_grad(edge_weight):
+            fused = _concat_fused_training if AG.needs_grad(x, ws, wn, bias) else _concat_fused
+            h = fused(x, plan, w_csr, ws, wn, bias, activation, normalize, op, None)
+            if h is not None:
+                return h
+        reduced = AG.aggregate(plan, x, op, w_csr) if AG.needs_grad(x, edge_weight) else segment_reduce(plan, x, op, w_csr=w_csr)
+        return _combine(ws, x, wn, reduced, bias, activation, concat, normalize)
     if not ku_n < F:
         if concat and not AG.needs_grad(x, edge_weight, ws, wn, bias):
             h = _concat_fused(x, *_graph(x, edge_index, edge_weight, cache), ws, wn, bias, activation, normalize, op, cache)

@@ -348,9 +348,14 @@ class HalfRows(object):
     autograd.aggregate / aggregate_neighbors / SparseMatrix @ / the mean and sum GraphSAGE layers take it in place of a
     float32 tensor and run tfgx_segment_reduce_h16 (include/tfgx_h16.h): a gathered row touches half the 128-byte lines,
     and the result is, bit for bit, what the float32 route returns for .float().  Opt-in: a plain 16-bit torch.Tensor is
-    still widened by _lib.as_f32 and takes the float32 kernel."""
+    still widened by _lib.as_f32 and takes the float32 kernel.
 
-    def __init__(self, table, F, source=None):
+    gemm_operand=True declares the table for the GEMM position as well: gemm_bias_act / gemm_tn and, through them, the
+    GEMM-first layers (GCN with units <= F, GAT, the self half and the narrow route of mean / sum GraphSAGE) read it with
+    tfgx_gemm_bias_act_cols_ws_h16 / tfgx_gemm_tn_gated_h16 (include/tfgx_gemm_h16.h) — the float32 GEMM's bits for .float(),
+    no widened copy.  Without it those layers refuse the table as before."""
+
+    def __init__(self, table, F, source=None, gemm_operand=False):
         assert isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype in L.H16_DTYPES, \
             "HalfRows: a 2-D torch.bfloat16 / torch.float16 tensor"
         F = int(F)
@@ -364,6 +369,7 @@ class HalfRows(object):
         self.shape = (int(table.shape[0]), F)
         self.dtype, self.device = table.dtype, table.device
         self.source = source          # from_tensor: the caller's 16-bit tensor, which receives d/dx
+        self.gemm_operand = bool(gemm_operand)
 
     @property
     def requires_grad(self):
@@ -385,7 +391,7 @@ class HalfRows(object):
         return HalfRows(torch.empty((int(n), ld), dtype=dtype, device=device), F)
 
     @staticmethod
-    def from_dense(x, dtype=torch.bfloat16, ld=None, out=None):
+    def from_dense(x, dtype=torch.bfloat16, ld=None, out=None, gemm_operand=False):
         """Quantise a float32 [n, F] tensor (tfgx_rows_f32_to_h16: round to nearest even) into `out` or a new table."""
         lib = L.require_gpu()
         if dtype not in L.H16_DTYPES:
@@ -394,12 +400,13 @@ class HalfRows(object):
         n, F = int(x.shape[0]), int(x.shape[1])
         h = HalfRows.empty(n, F, dtype, x.device, ld) if out is None else out
         assert h.shape == (n, F) and h.dtype == dtype
+        h.gemm_operand = h.gemm_operand or bool(gemm_operand)
         L.check(lib.tfgx_rows_f32_to_h16(L.ptr(x), ldx, n, F, L.ptr(h.table), h.ld, L.H16_DTYPES[dtype], L.stream_ptr()),
                 "tfgx_rows_f32_to_h16")
         return h
 
     @staticmethod
-    def from_tensor(t):
+    def from_tensor(t, gemm_operand=False):
         """A HalfRows over a 16-bit torch tensor [n, F] that may require grad: autograd.aggregate on it hands t the float32
         gradient rounded to t.dtype.  The tensor itself is the table when its rows are 16-byte aligned, else its values are
         copied onto the friendly stride."""
@@ -414,7 +421,7 @@ class HalfRows(object):
             buf = torch.empty((n, h16_friendly_ld(F)), dtype=d.dtype, device=dev)
             buf[:, :F].copy_(d)
             d = buf
-        return HalfRows(d, F, source=t if t.requires_grad else None)
+        return HalfRows(d, F, source=t if t.requires_grad else None, gemm_operand=gemm_operand)
 
 
 def _h16_avg_lines(F, ld):
@@ -1326,11 +1333,17 @@ def gather_friendly_copy(t):
 
 
 def gemm_bias_act(a, b, bias=None, act=L.ACT_NONE, out=None, act_cols=None):
-    """act(a @ b + bias) on the fp32 MFMA kernel; `act_cols`: activate only columns [0, act_cols)."""
+    """act(a @ b + bias) on the fp32 MFMA kernel; `act_cols`: activate only columns [0, act_cols).  `a`: a float32 tensor, or
+    a HalfRows (a 16-bit table) — tfgx_gemm_bias_act_cols_ws_h16: the table is read as it is (nothing is widened) and the
+    result is, bit for bit, what this function returns for a.float()."""
     lib = L.require_gpu()
-    a, lda = L.row_major_2d(L.as_f32(a))
+    half = a if isinstance(a, HalfRows) else None
+    if half is not None:
+        a, lda = half.table, half.ld
+    else:
+        a, lda = L.row_major_2d(L.as_f32(a))
     b, ldb = L.row_major_2d(L.as_f32(b))
-    M, K = int(a.shape[0]), int(a.shape[1])
+    M, K = (half.shape if half is not None else (int(a.shape[0]), int(a.shape[1])))
     if int(b.shape[0]) != K:
         raise ValueError("matmul shape mismatch: {} @ {}".format(tuple(a.shape), tuple(b.shape)))
     N = int(b.shape[1])
@@ -1341,9 +1354,14 @@ def gemm_bias_act(a, b, bias=None, act=L.ACT_NONE, out=None, act_cols=None):
     bias_t = None if bias is None else L.as_f32(bias).contiguous()
     ws_bytes = lib.tfgx_gemm_workspace_bytes(M, K, N)       # split-K partials (small M, long K) or the row kernel's tile counters (tall M)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
-    L.check(lib.tfgx_gemm_bias_act_cols_ws_f32(L.ptr(a), lda, L.ptr(b), ldb, L.ptr(bias_t), act,
-                                               N if act_cols is None else int(act_cols), L.ptr(out), ldc, M, K, N,
-                                               L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_bias_act_cols_ws_f32")
+    if half is not None:
+        L.check(lib.tfgx_gemm_bias_act_cols_ws_h16(L.ptr(a), L.H16_DTYPES[half.dtype], lda, L.ptr(b), ldb, L.ptr(bias_t), act,
+                                                   N if act_cols is None else int(act_cols), L.ptr(out), ldc, M, K, N,
+                                                   L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_bias_act_cols_ws_h16")
+    else:
+        L.check(lib.tfgx_gemm_bias_act_cols_ws_f32(L.ptr(a), lda, L.ptr(b), ldb, L.ptr(bias_t), act,
+                                                   N if act_cols is None else int(act_cols), L.ptr(out), ldc, M, K, N,
+                                                   L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_bias_act_cols_ws_f32")
     if given:
         written_by_kernel(out)
     return out
@@ -1377,11 +1395,17 @@ def gather_rows(x, idx, out=None):
 def gemm_tn(x, g, want_bias=False, gate=None):
     """(x^T @ g, column sums of g or None): the weight / bias gradient of a dense layer on the MFMA reduction kernel
     (tfgx_gemm_tn_f32).  x [M, Ka], g [M, N] -> dW [Ka, N], db [N].  `gate` [M, N]: count g only where gate > 0 (the
-    ReLU of the layer's epilogue, gate = the layer's output) — the masked gradient is never materialised."""
+    ReLU of the layer's epilogue, gate = the layer's output) — the masked gradient is never materialised.  `x`: a float32
+    tensor, or a HalfRows read as it is by tfgx_gemm_tn_gated_h16 (the bits of this function on x.float())."""
     lib = L.require_gpu()
-    x, ldx = L.row_major_2d(L.as_f32(x))
+    half = x if isinstance(x, HalfRows) else None
+    if half is not None:
+        x, ldx = half.table, half.ld
+    else:
+        x, ldx = L.row_major_2d(L.as_f32(x))
     g, ldg = L.row_major_2d(L.as_f32(g))
-    M, Ka, N = int(x.shape[0]), int(x.shape[1]), int(g.shape[1])
+    M, Ka = (half.shape if half is not None else (int(x.shape[0]), int(x.shape[1])))
+    N = int(g.shape[1])
     if int(g.shape[0]) != M:
         raise ValueError("gemm_tn: x has {} rows, g has {}".format(M, int(g.shape[0])))
     ldt = 0
@@ -1393,8 +1417,12 @@ def gemm_tn(x, g, want_bias=False, gate=None):
     db = torch.empty(N, dtype=torch.float32, device=x.device) if want_bias else None
     ws_bytes = lib.tfgx_gemm_tn_workspace_bytes(M, Ka, N, 1 if want_bias else 0)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-    L.check(lib.tfgx_gemm_tn_gated_f32(L.ptr(x), ldx, L.ptr(g), ldg, L.ptr(gate), ldt, M, Ka, N, L.ptr(dW), N, L.ptr(db),
-                                       L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_tn_gated_f32")
+    if half is not None:
+        L.check(lib.tfgx_gemm_tn_gated_h16(L.ptr(x), L.H16_DTYPES[half.dtype], ldx, L.ptr(g), ldg, L.ptr(gate), ldt, M, Ka, N,
+                                           L.ptr(dW), N, L.ptr(db), L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_tn_gated_h16")
+    else:
+        L.check(lib.tfgx_gemm_tn_gated_f32(L.ptr(x), ldx, L.ptr(g), ldg, L.ptr(gate), ldt, M, Ka, N, L.ptr(dW), N, L.ptr(db),
+                                           L.ptr(ws), ws_bytes, L.stream_ptr()), "tfgx_gemm_tn_gated_f32")
     return dW, db
 
 
