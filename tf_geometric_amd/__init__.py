@@ -18,6 +18,8 @@ from . import nn
 from . import layers
 from . import dist
 from . import utils
+from . import data
+from .data import Graph, BatchGraph
 from .graph_capture import CapturedForward, CapturedTrainStep
 
 

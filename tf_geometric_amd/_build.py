@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
-           "tfgx_normgrad.hip"]
+           "tfgx_normgrad.hip", "tfgx_collate.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -44,7 +44,8 @@ def build(force=False, verbose=True):
                                      os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],
                 "tfgx_asap.hip": [os.path.join(_HERE, "..", "include", "tfgx_asap.h")],
                 "tfgx_seggram.hip": [os.path.join(_HERE, "..", "include", "tfgx_seggram.h")],
-                "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")]}
+                "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")],
+                "tfgx_collate.hip": [os.path.join(_HERE, "..", "include", "tfgx_collate.h")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -382,6 +382,38 @@ NORMGRAD_SIGNATURES = {
                                                   _P, _P, _I32, _P]),
 }
 
+
+
+class CollatePlan(ctypes.Structure):
+    """struct tfgx_collate_plan (include/tfgx_collate.h)."""
+    _fields_ = [("ds_row_ptr", ctypes.c_void_p), ("ds_col", ctypes.c_void_p), ("ds_perm", ctypes.c_void_p),
+                ("out_row_ptr", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_perm", ctypes.c_void_p)]
+
+
+class CollateArgs(ctypes.Structure):
+    """struct tfgx_collate_args (include/tfgx_collate.h)."""
+    _fields_ = [
+        ("ds_x", ctypes.c_void_p), ("ds_ldx", ctypes.c_int64), ("F", ctypes.c_int64),
+        ("ds_row", ctypes.c_void_p), ("ds_col", ctypes.c_void_p), ("ds_w", ctypes.c_void_p),
+        ("ds_n", ctypes.c_int64), ("ds_e", ctypes.c_int64),
+        ("table", ctypes.c_void_p), ("B", ctypes.c_int64), ("n_out", ctypes.c_int64), ("e_out", ctypes.c_int64),
+        ("out_x", ctypes.c_void_p), ("out_ldx", ctypes.c_int64), ("out_node_graph_index", ctypes.c_void_p),
+        ("out_row", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_edge_graph_index", ctypes.c_void_p),
+        ("out_w", ctypes.c_void_p),
+        ("plan", ctypes.POINTER(CollatePlan)), ("plan_t", ctypes.POINTER(CollatePlan)),
+    ]
+
+
+# include/tfgx_collate.h (minibatch assembly out of a packed device dataset, with sort-free plans): its own header, version and
+# table — checked against that header by tests/test_collate_abi.py.
+COLLATE_ABI_VERSION = 1
+COLLATE_TILE = 1024          # TFGX_COLLATE_TILE: output elements per workgroup
+COLLATE_SIGNATURES = {
+    "tfgx_collate_version": (ctypes.c_int, []),
+    "tfgx_collate_tile": (ctypes.c_int, []),
+    "tfgx_collate": (ctypes.c_int, [ctypes.POINTER(CollateArgs), _P]),
+}
+
 _lib = None
 
 
@@ -445,6 +477,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in COLLATE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_collate_version() != COLLATE_ABI_VERSION or lib.tfgx_collate_tile() != COLLATE_TILE:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_collate ABI {} (tile {}) but this package binds {} (tile {}) "
+                        "(include/tfgx_collate.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_collate_version(), lib.tfgx_collate_tile(), COLLATE_ABI_VERSION, COLLATE_TILE))
     if lib.tfgx_normgrad_version() != NORMGRAD_ABI_VERSION:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_normgrad ABI {} but this package binds {} "
                         "(include/tfgx_normgrad.h): rebuild with __graft_entry__.build()".format(

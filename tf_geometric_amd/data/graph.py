@@ -1,0 +1,382 @@
+# coding=utf-8
+"""Graph / BatchGraph: the containers every graph-classification demo of the reference starts from
+(tf_geometric/data/graph.py:20-620), with torch tensors where the reference has TF tensors and numpy kept as numpy.
+tensor_spec_* is TensorFlow-only and is left out; sparse x is not supported."""
+import types
+import warnings
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+
+def _get_shape(data):
+    return None if data is None else tuple(data.shape)
+
+
+def _is_tensor(data):
+    return isinstance(data, torch.Tensor)
+
+
+def _tensor_device():
+    """Where convert_data_to_tensor puts data: the current GPU; without one the containers still work, on CPU tensors (the
+    operators that take them do not: _lib.require_gpu)."""
+    return L.device() if torch.cuda.is_available() else torch.device("cpu")
+
+
+def _take(data, index):
+    """data[index] along the first axis for numpy and tensors alike."""
+    if _is_tensor(data):
+        return data.index_select(0, torch.as_tensor(index, device=data.device).long())
+    return np.asarray(data)[np.asarray(index)]
+
+
+class Graph(object):
+    """
+    A Graph object wrappers all the data of a graph,
+    including node features, edge info (index and weight) and graph label
+    """
+
+    def __init__(self, x, edge_index, y=None, edge_weight=None):
+        """
+        :param x: Tensor/NDArray/list, shape: [num_nodes, num_features], node features, or a zero-argument function
+            that returns them (evaluated at every access of ``graph.x``, :139-143).
+        :param edge_index: Tensor/NDArray/list, shape: [2, num_edges].  Each column (u, v) is a directed edge.
+        :param y: Tensor/NDArray/list/None, any shape, graph label.  To build a BatchGraph out of graphs, y cannot be a scalar.
+        :param edge_weight: Tensor/NDArray/list/None, shape: [num_edges]; ones when absent (:50-56).
+        """
+        self._x = Graph.cast_x(x)
+        self.edge_index = Graph.cast_edge_index(edge_index)
+        self.y = Graph.cast_y(y)
+        self.cache = {}
+
+        if edge_weight is not None:
+            self.edge_weight = self.cast_edge_weight(edge_weight)
+        elif _is_tensor(self.edge_index):
+            self.edge_weight = torch.ones([self.num_edges], dtype=torch.float32, device=self.edge_index.device)
+        else:
+            self.edge_weight = np.ones([self.num_edges], dtype=np.float32)
+
+    @classmethod
+    def cast_edge_index(cls, x):
+        if isinstance(x, list):
+            x = np.array(x).astype(np.int32)
+        elif isinstance(x, np.ndarray):
+            x = x.astype(np.int32)
+        elif _is_tensor(x):
+            x = x.to(torch.int32)
+        return x
+
+    @classmethod
+    def cast_edge_weight(cls, edge_weight):
+        if isinstance(edge_weight, list):
+            edge_weight = np.array(edge_weight).astype(np.float32)
+        elif isinstance(edge_weight, np.ndarray):
+            edge_weight = edge_weight.astype(np.float32)
+        elif _is_tensor(edge_weight) and not isinstance(edge_weight, torch.nn.Parameter):
+            edge_weight = edge_weight.to(torch.float32)
+        return edge_weight
+
+    @classmethod
+    def cast_x(cls, x):
+        if isinstance(x, list):
+            x = np.array(x)
+        if isinstance(x, np.ndarray) and x.dtype == np.float64:
+            x = x.astype(np.float32)
+        elif _is_tensor(x) and not isinstance(x, torch.nn.Parameter) and x.dtype == torch.float64:
+            x = x.to(torch.float32)
+        return x
+
+    @classmethod
+    def cast_y(cls, y):
+        if isinstance(y, list):
+            y = np.array(y)
+        return y
+
+    @property
+    def x(self):
+        if isinstance(self._x, types.FunctionType):
+            return self._x()
+        return self._x
+
+    @property
+    def num_nodes(self):
+        return len(self.x)
+
+    @property
+    def num_edges(self):
+        """Number of edges; 0 for an empty list (``[]`` or shape [0]) as well as for shape [2, 0]."""
+        if _is_tensor(self.edge_index):
+            return 0 if self.edge_index.shape[0] == 0 else int(self.edge_index.shape[1])
+        if len(self.edge_index) == 0:
+            return 0
+        return len(self.edge_index[0])
+
+    @property
+    def num_features(self):
+        return self.x.shape[-1]
+
+    def get_shape_desc(self):
+        return "Graph Shape: x => {}\tedge_index => {}\ty => {}".format(
+            _get_shape(self.x), _get_shape(self.edge_index), _get_shape(self.y))
+
+    def __str__(self):
+        return self.get_shape_desc()
+
+    def __repr__(self):
+        return self.__str__()
+
+    def adj(self):
+        """The [num_nodes, num_nodes] adjacency as this package's SparseMatrix (tf_sparse.SparseMatrix in the reference)."""
+        from ..sparse import SparseMatrix
+        num_nodes = self.num_nodes
+        return SparseMatrix(self.edge_index, self.edge_weight, shape=[num_nodes, num_nodes])
+
+    def _inplace_convert_data_to_tensor(self, keys):
+        dev = _tensor_device()
+        for key in keys:
+            data = getattr(self, key)
+            if data is not None and not _is_tensor(data) and not isinstance(data, types.FunctionType):
+                setattr(self, key, torch.from_numpy(np.ascontiguousarray(np.asarray(data))).to(dev))
+        return self
+
+    def convert_data_to_tensor(self, inplace=False):
+        """Convert all graph data into device tensors.  inplace=False returns a new Graph and leaves this one alone."""
+        if inplace:
+            graph = self
+        else:
+            graph = Graph(self._x, self.edge_index, y=self.y, edge_weight=self.edge_weight)
+        graph._inplace_convert_data_to_tensor(["_x", "edge_index", "edge_weight", "y"])
+        return graph
+
+    def to_directed(self, merge_mode="sum", inplace=False):
+        """(u, v) -> (u, v) and (v, u), duplicates merged with `merge_mode` (tfg.utils.convert_edge_to_directed).
+
+        :return: If inplace is False, a new graph with directed edges; else this graph, changed."""
+        from ..utils import convert_edge_to_directed
+        edge_index, [edge_weight] = convert_edge_to_directed(self.edge_index, [self.edge_weight], merge_modes=[merge_mode])
+        if inplace:
+            self.edge_index, self.edge_weight = edge_index, edge_weight
+            return self
+        return Graph(self.x, edge_index, y=self.y, edge_weight=edge_weight)
+
+    def convert_edge_to_directed(self, merge_mode="sum"):
+        """.. deprecated:: Use ``to_directed(inplace=True)`` instead."""
+        warnings.warn(
+            "'Graph.convert_edge_to_directed(self, merge_mode)' is deprecated, use 'Graph.to_directed(inplace=True)' instead",
+            DeprecationWarning)
+        return self.to_directed(merge_mode, inplace=True)
+
+    def sample_new_graph_by_node_index(self, sampled_node_index):
+        """A new graph of the nodes in `sampled_node_index` (renumbered by their position in it) and the edges between them
+        (tfg.utils.sample_new_graph_by_node_index); x, y and, for a BatchGraph, node_graph_index are gathered per node."""
+        from ..utils import sample_new_graph_by_node_index
+        is_batch_graph = isinstance(self, BatchGraph)
+        x, edge_index, edge_weight, node_graph_index = sample_new_graph_by_node_index(
+            self.edge_index, sampled_node_index, x=self.x, edge_weight=self.edge_weight,
+            node_graph_index=self.node_graph_index if is_batch_graph else None)
+        idx = sampled_node_index.cpu().numpy() if _is_tensor(sampled_node_index) else np.asarray(sampled_node_index)
+        y = None if self.y is None else _take(self.y, idx)
+        if not is_batch_graph:
+            return Graph(x=x, edge_index=edge_index, y=y, edge_weight=edge_weight)
+        # an edge lies inside one graph: its graph is the graph of its first endpoint
+        if _is_tensor(edge_index):
+            edge_graph_index = torch.as_tensor(node_graph_index, device=edge_index.device).to(torch.int32)[edge_index[0].long()]
+        else:
+            ngi = node_graph_index.cpu().numpy() if _is_tensor(node_graph_index) else np.asarray(node_graph_index)
+            edge_graph_index = ngi.astype(np.int32)[edge_index[0]]
+        return BatchGraph(x=x, edge_index=edge_index, node_graph_index=node_graph_index, edge_graph_index=edge_graph_index,
+                          y=y, edge_weight=edge_weight)
+
+
+class BatchGraph(Graph):
+    """
+    Batch graph wrap a batch of graphs into a single graph, where each nodes has an unique index and a graph index.
+    The node_graph_index is the index of the corresponding graph for each node in the batch.
+    The edge_graph_index is the index of the corresponding graph for each edge in the batch.
+
+    Two deviations from the reference:
+
+    - ``num_graphs``: a batch made by ``from_graphs`` or by ``GraphStore.collate`` knows its graph count, so trailing graphs
+      without nodes are counted.  Only a hand-constructed batch falls back to ``max(node_graph_index) + 1`` (the reference's
+      rule everywhere).
+    - ``to_graphs`` / ``reorder``: ``y`` is split per node when it has ``num_nodes`` rows and per graph when it has
+      ``num_graphs != num_nodes`` rows; anything else raises ``ValueError``.  (The reference gathers every ``y`` with the node
+      sort index, which for the per-graph ``y`` that ``from_graphs`` itself produces is an index error.)
+    """
+
+    def __init__(self, x, edge_index, node_graph_index, edge_graph_index, y=None, edge_weight=None, graphs=None):
+        super().__init__(x, edge_index, y, edge_weight)
+        self.node_graph_index = node_graph_index
+        self.edge_graph_index = edge_graph_index
+        self.graphs = graphs
+        self._num_graphs = None if graphs is None else len(graphs)
+
+    @property
+    def num_graphs(self):
+        if self._num_graphs is not None:
+            return self._num_graphs
+        if len(self.node_graph_index) == 0:
+            return 0
+        if _is_tensor(self.node_graph_index):
+            return int(self.node_graph_index.max().item()) + 1
+        return int(np.max(self.node_graph_index)) + 1
+
+    def _y_rows(self, num_graphs):
+        """"node" / "graph" / None: how y is laid out (see the class docstring)."""
+        if self.y is None:
+            return None
+        rows = int(self.y.shape[0]) if len(self.y.shape) > 0 else -1
+        if rows == self.num_nodes:
+            return "node"
+        if rows == num_graphs:
+            return "graph"
+        raise ValueError("y has {} rows: neither one per node ({}) nor one per graph ({})".format(
+            max(rows, 0), self.num_nodes, num_graphs))
+
+    def reorder(self):
+        """Nodes and edges sorted (stably) by their graph index.  A per-node y follows the nodes, a per-graph y stays."""
+        num_graphs = self.num_graphs
+        if _is_tensor(self.node_graph_index):
+            node_sort_index = torch.argsort(self.node_graph_index.long(), stable=True)
+        else:
+            node_sort_index = np.argsort(np.asarray(self.node_graph_index), kind="stable")
+        if _is_tensor(self.edge_graph_index):
+            edge_sort_index = torch.argsort(self.edge_graph_index.long(), stable=True)
+        else:
+            edge_sort_index = np.argsort(np.asarray(self.edge_graph_index), kind="stable")
+
+        def to_index(index, like):      # an index of the kind `like` understands
+            if _is_tensor(like):
+                return torch.as_tensor(index, device=like.device)
+            return index.cpu().numpy() if _is_tensor(index) else index
+
+        node_graph_index = _take(self.node_graph_index, to_index(node_sort_index, self.node_graph_index))
+        x = _take(self.x, to_index(node_sort_index, self.x))
+        y = self.y
+        if self._y_rows(num_graphs) == "node":
+            y = _take(self.y, to_index(node_sort_index, self.y))
+        edge_graph_index = _take(self.edge_graph_index, to_index(edge_sort_index, self.edge_graph_index))
+        es = to_index(edge_sort_index, self.edge_index)
+        edge_index = self.edge_index.index_select(1, es.long()) if _is_tensor(self.edge_index) else self.edge_index[:, es]
+        edge_weight = None if self.edge_weight is None else _take(self.edge_weight, to_index(edge_sort_index, self.edge_weight))
+        batch = BatchGraph(x, edge_index, node_graph_index, edge_graph_index, y=y, edge_weight=edge_weight)
+        batch._num_graphs = num_graphs
+        return batch
+
+    def to_graphs(self):
+        batch_graph = self.reorder()
+        num_graphs = batch_graph.num_graphs
+        y_rows = batch_graph._y_rows(num_graphs)
+
+        def host(index):
+            return index.cpu().numpy() if _is_tensor(index) else np.asarray(index)
+
+        num_nodes_list = np.bincount(host(batch_graph.node_graph_index).astype(np.int64), minlength=num_graphs)
+        num_edges_list = np.bincount(host(batch_graph.edge_graph_index).astype(np.int64), minlength=num_graphs)
+        nodes_before = np.concatenate([[0], np.cumsum(num_nodes_list)]).astype(np.int64).tolist()
+        edges_before = np.concatenate([[0], np.cumsum(num_edges_list)]).astype(np.int64).tolist()
+
+        graphs = []
+        for i in range(num_graphs):
+            x = batch_graph.x[nodes_before[i]: nodes_before[i + 1]]
+            if y_rows is None:
+                y = None
+            elif y_rows == "node":
+                y = batch_graph.y[nodes_before[i]: nodes_before[i + 1]]
+            else:
+                y = batch_graph.y[i: i + 1]
+            edge_index = batch_graph.edge_index[:, edges_before[i]:edges_before[i + 1]] - nodes_before[i]
+            edge_weight = None if batch_graph.edge_weight is None else batch_graph.edge_weight[edges_before[i]:edges_before[i + 1]]
+            graphs.append(Graph(x=x, edge_index=edge_index, y=y, edge_weight=edge_weight))
+        return graphs
+
+    @classmethod
+    def from_graphs(cls, graphs):
+        """numpy graphs give numpy arrays, array for array what the reference gives; tensor graphs are joined with torch.cat."""
+        return BatchGraph(x=BatchGraph.build_x(graphs), edge_index=BatchGraph.build_edge_index(graphs),
+                          node_graph_index=BatchGraph.build_node_graph_index(graphs),
+                          edge_graph_index=BatchGraph.build_edge_graph_index(graphs), graphs=graphs,
+                          y=BatchGraph.build_y(graphs), edge_weight=BatchGraph.build_edge_weight(graphs))
+
+    @classmethod
+    def _build_graph_index(cls, graphs, counts):
+        first = graphs[0].edge_index
+        if _is_tensor(first):
+            return torch.cat([torch.full([c], i, dtype=torch.int32, device=first.device) for i, c in enumerate(counts)], dim=0)
+        return np.concatenate([np.full([c], i, dtype=np.int32) for i, c in enumerate(counts)], axis=0)
+
+    @classmethod
+    def build_node_graph_index(cls, graphs):
+        return cls._build_graph_index(graphs, [graph.num_nodes for graph in graphs])
+
+    @classmethod
+    def build_edge_graph_index(cls, graphs):
+        return cls._build_graph_index(graphs, [graph.num_edges for graph in graphs])
+
+    @classmethod
+    def _concat(cls, parts, axis=0):
+        if _is_tensor(parts[0]):
+            return torch.cat(parts, dim=axis)
+        return np.concatenate(parts, axis=axis)
+
+    @classmethod
+    def build_x(cls, graphs):
+        return cls._concat([graph.x for graph in graphs])
+
+    @classmethod
+    def build_edge_index(cls, graphs):
+        edge_index_list = []
+        num_history_nodes = 0
+        for graph in graphs:
+            edge_index_list.append(graph.edge_index + num_history_nodes)
+            num_history_nodes += graph.num_nodes
+        return cls._concat(edge_index_list, axis=1)
+
+    @classmethod
+    def build_edge_weight(cls, graphs):
+        if graphs[0].edge_weight is None:
+            return None
+        return cls._concat([graph.edge_weight for graph in graphs])
+
+    @classmethod
+    def build_y(cls, graphs):
+        if graphs[0].y is None:
+            return None
+        return cls._concat([graph.y for graph in graphs])
+
+    def convert_data_to_tensor(self, inplace=False):
+        """Convert all graph data into device tensors.  inplace=False returns a new BatchGraph and leaves this one alone."""
+        if inplace:
+            graph = self
+        else:
+            graph = BatchGraph(self._x, self.edge_index, self.node_graph_index, self.edge_graph_index, y=self.y,
+                               edge_weight=self.edge_weight, graphs=self.graphs)
+            graph._num_graphs = self._num_graphs
+        return graph._inplace_convert_data_to_tensor(["_x", "edge_index", "edge_weight", "y", "node_graph_index",
+                                                      "edge_graph_index"])
+
+    def to_directed(self, merge_mode="sum", inplace=False):
+        """As Graph.to_directed; edge_graph_index is merged with "max" (all copies of an edge lie in one graph)."""
+        from ..utils import convert_edge_to_directed
+        edge_index, [edge_weight, edge_graph_index] = convert_edge_to_directed(
+            self.edge_index, [self.edge_weight, self.edge_graph_index], merge_modes=[merge_mode, "max"])
+        # the merge runs in float32: graph ids come back as exact small floats
+        if _is_tensor(edge_graph_index):
+            edge_graph_index = edge_graph_index.to(torch.int32)
+        else:
+            edge_graph_index = np.asarray(edge_graph_index).astype(np.int32)
+        if inplace:
+            self.edge_index, self.edge_weight, self.edge_graph_index = edge_index, edge_weight, edge_graph_index
+            return self
+        batch = BatchGraph(self.x, edge_index, self.node_graph_index, edge_graph_index, y=self.y, edge_weight=edge_weight)
+        batch._num_graphs = self._num_graphs
+        return batch
+
+    def convert_edge_to_directed(self, merge_mode="sum"):
+        """.. deprecated:: Use ``to_directed(inplace=True)`` instead."""
+        warnings.warn(
+            "'BatchGraph.convert_edge_to_directed(self, merge_mode)' is deprecated, use 'BatchGraph.to_directed(inplace=True)' instead",
+            DeprecationWarning)
+        return self.to_directed(merge_mode, inplace=True)
