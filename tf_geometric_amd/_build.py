@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
-           "tfgx_normgrad.hip", "tfgx_collate.hip"]
+           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -32,7 +32,10 @@ def build(force=False, verbose=True):
     # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
     fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
     gemm_hdrs = [os.path.join(CSRC, "tfgx_gemm_kernels.h"), os.path.join(CSRC, "tfgx_mfma.h")]      # the GEMM templates both GEMM sources instantiate
+    sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's per-row bodies: both samplers are compiled from it
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
+                "tfgx_misc.hip": [sample_hdr],
+                "tfgx_nbrblock.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
                 "tfgx_gemm.hip": gemm_hdrs,
                 "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
                 "tfgx_fused.hip": fused_hdrs,
@@ -210,7 +213,8 @@ def build_asan(force=False, verbose=True):
     tests/test_abi.py::test_host_code_under_address_sanitizer and tools/asan_host_check.py."""
     os.makedirs(ASAN_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC, x) for x in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "tfgx_common.h"), os.path.join(_HERE, "..", "include", "tfgx.h")]
+    deps = srcs + [os.path.join(CSRC, "tfgx_common.h"), os.path.join(CSRC, "tfgx_sample_rows.h"),
+                   os.path.join(_HERE, "..", "include", "tfgx.h")]
     if not force and os.path.exists(ASAN_LIB) and not any(_newer(d, ASAN_LIB) for d in deps):
         return ASAN_LIB
     flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",

@@ -414,6 +414,20 @@ COLLATE_SIGNATURES = {
     "tfgx_collate": (ctypes.c_int, [ctypes.POINTER(CollateArgs), _P]),
 }
 
+# include/tfgx_nbrblock.h (minibatch neighbour sampling: the row-list sampler and the order-stable relabel over a persistent
+# table): its own header, version and table — checked against that header by tests/test_nbrblock_abi.py.
+NBRBLOCK_ABI_VERSION = 1
+NBRBLOCK_EMPTY = (1 << 31) - 1     # TFGX_NBRBLOCK_EMPTY: a table entry without a virtual id
+NBRBLOCK_BAD_RANGE, NBRBLOCK_BAD_REPEAT = 1, 2
+NBRBLOCK_SIGNATURES = {
+    "tfgx_nbrblock_version": (ctypes.c_int, []),
+    "tfgx_nbrblock_sample_rows": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I32, _U64, _P, _P, _P, _P]),
+    "tfgx_nbrblock_stamp": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
+    "tfgx_nbrblock_relabel_workspace_bytes": (_SZ, [_I64]),
+    "tfgx_nbrblock_relabel": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "tfgx_nbrblock_reset": (ctypes.c_int, [_P, _I64, _P, _I64, _P]),
+}
+
 _lib = None
 
 
@@ -481,6 +495,14 @@ def load_library():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in NBRBLOCK_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.tfgx_nbrblock_version() != NBRBLOCK_ABI_VERSION:
+        raise TfgxError("tf_geometric_amd: {} was built for tfgx_nbrblock ABI {} but this package binds {} "
+                        "(include/tfgx_nbrblock.h): rebuild with __graft_entry__.build()".format(
+                            LIB_PATH, lib.tfgx_nbrblock_version(), NBRBLOCK_ABI_VERSION))
     if lib.tfgx_collate_version() != COLLATE_ABI_VERSION or lib.tfgx_collate_tile() != COLLATE_TILE:
         raise TfgxError("tf_geometric_amd: {} was built for tfgx_collate ABI {} (tile {}) but this package binds {} (tile {}) "
                         "(include/tfgx_collate.h): rebuild with __graft_entry__.build()".format(

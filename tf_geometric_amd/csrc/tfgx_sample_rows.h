@@ -1,0 +1,122 @@
+// The neighbour sampler's generator and per-row bodies (RandomNeighborSampler.sample, tf_geometric/utils/graph_utils.py:667-772),
+// shared by the whole-graph sampler (tfgx_misc.hip: row r of the graph -> out row r) and the row-list sampler
+// (tfgx_nbrblock.hip: node rows[i] -> out row i).  A body is parameterised by the ROW ID that keys the generator and by the
+// OUTPUT OFFSET of the row; given the same (seed, row id, d, m, replace_when_short) both callers write the same bits.
+#pragma once
+#include "tfgx_common.h"
+
+namespace tfgx {
+
+// counter-based generator: a 64-bit mix of (seed, row, draw) — reproducible, order-independent, no state
+__device__ __forceinline__ uint32_t draw_u32(uint64_t seed, uint64_t row, uint32_t i)
+{
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (row * 0x100000001B3ull + i + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return static_cast<uint32_t>((z ^ (z >> 31)) >> 32);
+}
+__device__ __forceinline__ int draw_below(uint64_t seed, uint64_t row, uint32_t i, int n)   // uniform in [0, n)
+{
+    return static_cast<int>((uint64_t(draw_u32(seed, row, i)) * uint64_t(n)) >> 32);
+}
+
+constexpr int kSampleLongRow = 64;       // rows with more neighbours / draws than this get a whole wave (coalesced walks)
+
+constexpr int kFloydMax = 32;            // Floyd's O(m^2) duplicate check only for few draws; otherwise one O(d) selection pass
+
+__device__ __forceinline__ bool sample_row_is_long(int d, int m)
+{
+    return (d > kSampleLongRow && m > kFloydMax) || m > kSampleLongRow;
+}
+
+// ONE LANE samples m > 0 of the d neighbours at CSR positions [s, s + d) of row `r` into out_col / out_w [o, o + m); the row
+// is not long (sample_row_is_long(d, m) is false)
+__device__ __forceinline__ void sample_row_lane(const int32_t* __restrict__ col, const float* __restrict__ w, uint64_t r,
+                                                int s, int d, int o, int m, int replace_when_short, uint64_t seed,
+                                                int32_t* __restrict__ out_col, float* __restrict__ out_w)
+{
+    if (m >= d && !(replace_when_short && m > d)) {          // keep every neighbour, in order (:742-744)
+        for (int i = 0; i < d; ++i) {
+            out_col[o + i] = col[s + i];
+            if (out_w) out_w[o + i] = w ? w[s + i] : 1.0f;
+        }
+        return;
+    }
+    if (m > d) {                                             // padding: m draws WITH replacement (:749)
+        for (int i = 0; i < m; ++i) {
+            const int t = draw_below(seed, r, uint32_t(i), d);
+            out_col[o + i] = col[s + t];
+            if (out_w) out_w[o + i] = w ? w[s + t] : 1.0f;
+        }
+        return;
+    }
+    if (m > kFloydMax) {
+        // m < d, more than a few draws (ratio sampling): Knuth's selection sampling (Algorithm S) — one pass over
+        // the d neighbours, position j is taken with probability (m - taken) / (d - j): uniform without replacement,
+        // no scratch, neighbour order kept
+        int taken = 0;
+        for (int j = 0; j < d && taken < m; ++j) {
+            if (draw_below(seed, r, uint32_t(j), d - j) < m - taken) {
+                out_col[o + taken] = col[s + j];
+                if (out_w) out_w[o + taken] = w ? w[s + j] : 1.0f;
+                ++taken;
+            }
+        }
+        return;
+    }
+    // m < d: Floyd's algorithm — m distinct positions of [0, d) with uniform probability, no replacement
+    int chosen[kFloydMax];
+    int c = 0;
+    for (int j = d - m; j < d; ++j) {
+        int t = draw_below(seed, r, uint32_t(j - (d - m)), j + 1);
+        bool dup = false;
+        for (int q = 0; q < c; ++q) dup |= (chosen[q] == t);
+        chosen[c++] = dup ? j : t;
+    }
+    for (int i = 0; i < m; ++i) {
+        out_col[o + i] = col[s + chosen[i]];
+        if (out_w) out_w[o + i] = w ? w[s + chosen[i]] : 1.0f;
+    }
+}
+
+// ONE WAVE (all 64 lanes, `lane` = the caller's lane id) samples a LONG row (sample_row_is_long(d, m), m > 0).
+// keep-all and with-replacement rows are copied / drawn lane-parallel.  m < d: the row's d positions are cut into 64
+// contiguous strata; with ONE uniform integer U in [0, d) per row, stratum [b0, b1) receives (m*b1 + U)/d - (m*b0 + U)/d of
+// the m samples (integer divisions: never more than it holds, exactly m in total, output offsets in closed form, expectation
+// m * len / d) and draws them by selection sampling (Algorithm S).  Neighbour order is kept and EVERY neighbour is included
+// with probability exactly m / d, as with the reference's np.random.choice; the joint draw is systematic across strata rather
+// than a uniform m-subset (lower variance).
+__device__ __forceinline__ void sample_row_wave(const int32_t* __restrict__ col, const float* __restrict__ w, uint64_t r,
+                                                int s, int d, int o, int m, int replace_when_short, uint64_t seed,
+                                                int32_t* __restrict__ out_col, float* __restrict__ out_w, int lane)
+{
+    constexpr int WV = 64;
+    if (m >= d && !(replace_when_short && m > d)) {          // keep every neighbour, in order
+        for (int i = lane; i < d; i += WV) {
+            out_col[o + i] = col[s + i];
+            if (out_w) out_w[o + i] = w ? w[s + i] : 1.0f;
+        }
+        return;
+    }
+    if (m > d) {                                             // padding: m draws WITH replacement (same draws as one lane)
+        for (int i = lane; i < m; i += WV) {
+            const int t = draw_below(seed, r, uint32_t(i), d);
+            out_col[o + i] = col[s + t];
+            if (out_w) out_w[o + i] = w ? w[s + t] : 1.0f;
+        }
+        return;
+    }
+    const int b0 = int(int64_t(d) * lane / WV), b1 = int(int64_t(d) * (lane + 1) / WV);        // stratum [b0, b1)
+    const int64_t U = draw_below(seed, r, 0xFFFFFFFFu, d);                                     // the row's random offset
+    const int o0 = int((int64_t(m) * b0 + U) / d), ml = int((int64_t(m) * b1 + U) / d) - o0;   // its samples
+    int taken = 0;
+    for (int j = b0; j < b1 && taken < ml; ++j) {
+        if (draw_below(seed, r, uint32_t(j), b1 - j) < ml - taken) {
+            out_col[o + o0 + taken] = col[s + j];
+            if (out_w) out_w[o + o0 + taken] = w ? w[s + j] : 1.0f;
+            ++taken;
+        }
+    }
+}
+
+}  // namespace tfgx

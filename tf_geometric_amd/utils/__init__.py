@@ -8,6 +8,7 @@ from .. import _lib as L
 from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
 from .link import (negative_sampling, negative_sampling_with_start_node, edge_train_test_split, extract_unique_edge,
                    convert_edge_index_to_edge_hash, convert_edge_hash_to_edge_index, sorted_adjacency)
+from .minibatch import SampledMinibatch, SampledBlock, hop_seed
 
 
 def add_self_loop_edge(edge_index, num_nodes, edge_weight=None, fill_weight=1.0):
@@ -234,6 +235,32 @@ class RandomNeighborSampler(object):
             n_cols = self.num_col_nodes if sampled_node_index is None else int(col.max().item()) + 1 if total else 0
             attach_plan(ei, CsrPlan.from_sorted(out_ptr, out_col, n_cols, edge_index=ei))
         return _out(ei, self._numpy), _out(out_w, self._numpy)
+
+    # ---- minibatch sampling (utils/minibatch.py, include/tfgx_nbrblock.h): work proportional to the batch ------------------
+    # One sampler serves ONE STREAM AT A TIME: sample_blocks writes to a table the sampler keeps between calls.
+
+    def sample_rows(self, rows, k=None, ratio=None, padding=False, seed=None):
+        """Sample neighbours of the listed nodes only: (edge_index [2, E], edge_weight [E]) with edge_index[0] the POSITION in
+        `rows` (non-decreasing) and edge_index[1] the global neighbour id.  Counts follow `sample` (min(deg, k); k where
+        padding and deg > 0; ceil(deg * ratio)) and are read from row_ptr[rows] alone.  With the same seed, row i holds exactly
+        what `sample` gives node rows[i] in the whole graph, whatever else is in the list (repeats allowed; ids past the last
+        row with an edge are nodes without neighbours).  Nothing sampled: a [2, 0] list, not None.  An id outside the graph:
+        ValueError (compared on the device, never used as an index).  `seed=None` draws one from torch's generator.  numpy in
+        (the sampler's edge_index) -> numpy out, as `sample`."""
+        from .minibatch import sample_rows
+        return sample_rows(self, rows, k=k, ratio=ratio, padding=padding, seed=seed)
+
+    def sample_blocks(self, seeds, fanouts, padding=False, seed=None):
+        """A minibatch for len(fanouts) layers as a SampledMinibatch: fanouts[l] neighbours per node for layer l (input side
+        first, as num_sampled_neighbors_list of the reference's demo), so sampling runs outward from the seeds with
+        fanouts[-1] first.  Hop h samples the rows node_index[:n_{h-1}] with seed hop_seeds[h-1] (minibatch.hop_seed) and
+        appends the neighbours not seen yet in first-occurrence order; mb.blocks[l] is the relabelled list of layer l with its
+        CSR plan attached.  Duplicate or out-of-range seeds: ValueError.  Device tensors out, whatever the sampler was built
+        from.  One host read per hop plus one for the seeds' verdict; refused inside a hipGraph capture.  The relabel table is
+        emptied at the end of every call; a call that raised midway leaves it marked and the next call refills it.
+        One sampler serves one stream at a time."""
+        from .minibatch import sample_blocks
+        return sample_blocks(self, seeds, fanouts, padding=padding, seed=seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------

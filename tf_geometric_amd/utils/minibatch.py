@@ -1,0 +1,282 @@
+# coding=utf-8
+"""Minibatch neighbour sampling on the device (include/tfgx_nbrblock.h): RandomNeighborSampler.sample_rows and
+RandomNeighborSampler.sample_blocks, and what they return.
+
+The reference trains GraphSAGE on sampled neighbourhoods (demo/demo_graph_sage.py: num_sampled_neighbors_list = [25, 10]) with
+a Python loop over nodes; here every hop is a handful of launches whose size is the batch: counts from row_ptr[rows], the
+row-list sampler (bit for bit the rows of RandomNeighborSampler.sample), and an order-stable relabel over a table the sampler
+keeps.  Nothing per call is proportional to the graph's nodes or edges."""
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .subgraph import refuse_capture
+
+_SEED_MASK = (1 << 63) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def hop_seed(seed, hop):
+    """The sampling seed of hop `hop` (0 = the hop next to the seeds): (seed + (hop + 1) * 0x9E3779B97F4A7C15) mod 2^63.
+    Distinct per hop, so a node that is a row in two hops does not draw the same neighbours twice; each value is a valid
+    `seed=` of RandomNeighborSampler.sample, which then reproduces the hop's rows."""
+    return (int(seed) + (int(hop) + 1) * _GOLDEN) & _SEED_MASK
+
+
+class SampledBlock(object):
+    """One hop as a layer sees it: edge_index int32 [2, E] = [position of the destination in the block; virtual id of the
+    sampled neighbour], edge_weight float32 [E], over num_src nodes of which the first num_dst are the destinations.
+    edge_index carries its CSR plan (plan.attach_plan): a layer called on x[:num_src] sorts nothing."""
+
+    def __init__(self, edge_index, edge_weight, num_dst, num_src):
+        self.edge_index = edge_index
+        self.edge_weight = edge_weight
+        self.num_dst = int(num_dst)
+        self.num_src = int(num_src)
+
+    @property
+    def num_edges(self):
+        return int(self.edge_index.shape[1])
+
+
+class SampledMinibatch(object):
+    """blocks[l] belongs to layer l (input side first); node_index int32 [n] are the global ids of the virtual nodes, the
+    seeds first and in the given order; hop_seeds are the per-hop sampling seeds (hop_seed); num_host_syncs counts the
+    device-to-host reads the call made.
+
+        h = mb.gather(x)
+        for layer, b in zip(layers, mb.blocks):
+            h = layer([h[:b.num_src], b.edge_index, b.edge_weight], training=True)[:b.num_dst]
+    """
+
+    def __init__(self, blocks, node_index, num_seeds, hop_seeds, num_host_syncs=0):
+        self.blocks = blocks
+        self.node_index = node_index
+        self.num_seeds = int(num_seeds)
+        self.hop_seeds = list(hop_seeds)
+        self.num_host_syncs = int(num_host_syncs)
+
+    def gather(self, x):
+        """x[node_index] for a float32 feature table [N, F] (tfgx_gather_rows_f32; a table that is being trained goes through
+        torch's indexing, which carries the gradient)."""
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.float32:
+                raise TypeError("SampledMinibatch.gather takes a float32 table, got {}".format(x.dtype))
+            if x.requires_grad and torch.is_grad_enabled():
+                return x[self.node_index.long()]
+        from ..plan import gather_rows
+        return gather_rows(L.as_f32(x), self.node_index)
+
+
+def _is_integral(ids):
+    if isinstance(ids, torch.Tensor):
+        return ids.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    return np.asarray(ids).dtype.kind in "iu" or np.asarray(ids).size == 0
+
+
+def _check_ids(ids, what):
+    if not _is_integral(ids):
+        raise ValueError("{} must be integers (node ids), got dtype {}".format(
+            what, ids.dtype if isinstance(ids, torch.Tensor) else np.asarray(ids).dtype))
+    shape = tuple(ids.shape) if isinstance(ids, torch.Tensor) else np.asarray(ids).shape
+    if len(shape) != 1:
+        raise ValueError("{} must be one-dimensional, got shape {}".format(what, shape))
+
+
+def check_sample_blocks_args(seeds, fanouts):
+    """The refusals of sample_blocks that need no device."""
+    if not isinstance(fanouts, (list, tuple)) or len(fanouts) == 0:
+        raise ValueError("fanouts must be a non-empty list of neighbour counts, one per layer (input side first)")
+    for f in fanouts:
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
+            raise ValueError("fanouts must be integers, got {!r}".format(f))
+        if f < 0:
+            raise ValueError("fanouts must not be negative, got {}".format(f))
+    _check_ids(seeds, "seeds")
+
+
+class _State(object):
+    """What a sampler keeps for the row-list calls: row_ptr padded to every node id (nodes that only appear as neighbours have
+    degree 0) and the relabel table, both made once."""
+
+    def __init__(self, sampler):
+        plan = sampler.plan
+        dev = plan.col.device
+        self.n_nodes = max(sampler.num_row_nodes, sampler.num_col_nodes)
+        tail = plan.row_ptr[-1:].expand(self.n_nodes - sampler.num_row_nodes)
+        self.row_ptr = torch.cat([plan.row_ptr, tail]).contiguous()
+        self.table = torch.full((self.n_nodes,), L.NBRBLOCK_EMPTY, dtype=torch.int32, device=dev)
+        self.dirty = False
+
+
+def _state(sampler):
+    st = getattr(sampler, "_nbrblock", None)
+    if st is None:
+        st = sampler._nbrblock = _State(sampler)
+    return st
+
+
+def _ids_on_device(ids, n_nodes, dev):
+    """(int32 ids, a device flag that is non-zero when an id wider than int32 was out of range before the cast)."""
+    t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids)))
+    t = t.detach().to(dev).reshape(-1)
+    if t.dtype == torch.int32:
+        return t.contiguous(), None
+    wide_bad = ((t < 0) | (t >= n_nodes)).any().to(torch.int32) if t.numel() else None
+    return t.to(torch.int32).contiguous(), wide_bad
+
+
+def _counts(deg, k, ratio, padding):
+    """Draws per row from its degree: the rules of RandomNeighborSampler.sample."""
+    if k is None and ratio is None:
+        return deg
+    if ratio is not None:
+        return torch.ceil(deg.to(torch.float64) * float(ratio)).to(torch.int32)
+    if padding:
+        return torch.where(deg > 0, torch.full_like(deg, int(k)), torch.zeros_like(deg))
+    return torch.clamp(deg, max=int(k))
+
+
+def _degrees(st, rows):
+    """deg[i] of node rows[i] from row_ptr[rows] alone; 0 for an id outside the graph (the kernels refuse those)."""
+    valid = (rows >= 0) & (rows < st.n_nodes)
+    r = torch.where(valid, rows, torch.zeros_like(rows)).long()
+    return torch.where(valid, st.row_ptr[r + 1] - st.row_ptr[r], torch.zeros_like(rows))
+
+
+def _out_ptr(cnt):
+    """(out_ptr int32 [n + 1], the total as a 0-d int64 device tensor)."""
+    n = int(cnt.shape[0])
+    out_ptr = torch.zeros(n + 1, dtype=torch.int32, device=cnt.device)
+    if n == 0:
+        return out_ptr, torch.zeros((), dtype=torch.int64, device=cnt.device)
+    csum = torch.cumsum(cnt, 0, dtype=torch.int64)
+    out_ptr[1:] = csum
+    return out_ptr, csum[-1]
+
+
+def _launch_sample(sampler, st, rows, n_rows, out_ptr, total, padding, seed, flag):
+    dev = rows.device
+    out_col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    out_w = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    L.check(L.load_library().tfgx_nbrblock_sample_rows(
+        L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(rows), n_rows, L.ptr(out_ptr),
+        1 if padding else 0, int(seed), L.ptr(out_col), L.ptr(out_w), L.ptr(flag), L.stream_ptr()),
+        "tfgx_nbrblock_sample_rows")
+    return out_col[:total], out_w[:total]
+
+
+def _row_positions(cnt, n_rows, total):
+    ar = torch.arange(n_rows, dtype=torch.int32, device=cnt.device)
+    return torch.repeat_interleave(ar, cnt.long(), output_size=total)
+
+
+def _check_total(total):
+    if total >= (1 << 31) - 1:
+        raise ValueError("the sample holds {} edges: more than int32 indexes".format(total))
+
+
+def sample_rows(sampler, rows, k=None, ratio=None, padding=False, seed=None):
+    if k is not None and ratio is not None:
+        raise Exception("k and ratio cannot be provided simultaneously")
+    _check_ids(rows, "rows")
+    L.require_gpu()
+    refuse_capture("RandomNeighborSampler.sample_rows")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    st = _state(sampler)
+    dev = st.table.device
+    rows_t, wide_bad = _ids_on_device(rows, st.n_nodes, dev)
+    n_rows = int(rows_t.shape[0])
+    if n_rows == 0:
+        ei = torch.zeros((2, 0), dtype=torch.int32, device=dev)
+        ew = torch.zeros(0, dtype=torch.float32, device=dev)
+        return (ei.cpu().numpy(), ew.cpu().numpy()) if sampler._numpy else (ei, ew)
+    cnt = _counts(_degrees(st, rows_t), k, ratio, padding)
+    out_ptr, total_dev = _out_ptr(cnt)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if wide_bad is not None:
+        flag |= wide_bad
+    total = int(total_dev.item())
+    _check_total(total)
+    out_col, out_w = _launch_sample(sampler, st, rows_t, n_rows, out_ptr, total, padding, seed, flag)
+    if int(flag.item()) != 0:
+        raise ValueError("sample_rows: a row id is outside [0, {})".format(st.n_nodes))
+    ei = torch.stack([_row_positions(cnt, n_rows, total), out_col])
+    if sampler._numpy:
+        return ei.cpu().numpy(), out_w.cpu().numpy()
+    return ei, out_w.contiguous()
+
+
+def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None):
+    from ..plan import CsrPlan, attach_plan
+    check_sample_blocks_args(seeds, fanouts)
+    lib = L.require_gpu()
+    refuse_capture("RandomNeighborSampler.sample_blocks")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    n_hops = len(fanouts)
+    hop_seeds = [hop_seed(seed, h) for h in range(n_hops)]
+    st = _state(sampler)
+    dev = st.table.device
+    if st.dirty:             # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
+        st.table.fill_(L.NBRBLOCK_EMPTY)
+    st.dirty = True          # until this call has reset what it wrote
+    stream = L.stream_ptr()
+    syncs = 0
+
+    node_list, wide_bad = _ids_on_device(seeds, st.n_nodes, dev)
+    num_seeds = n_known = int(node_list.shape[0])
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if wide_bad is not None:
+        flag |= wide_bad
+    L.check(lib.tfgx_nbrblock_stamp(L.ptr(st.table), st.n_nodes, L.ptr(node_list), n_known, 0, L.ptr(flag), stream),
+            "tfgx_nbrblock_stamp")
+    cnt = _counts(_degrees(st, node_list), int(fanouts[-1]), None, padding)
+    out_ptr, total_dev = _out_ptr(cnt)
+    bad, total = torch.stack([flag[0].long(), total_dev]).tolist()      # host read: the seeds' verdict and hop 1's edges
+    syncs += 1
+    if bad & L.NBRBLOCK_BAD_RANGE:
+        raise ValueError("sample_blocks: a seed is outside [0, {})".format(st.n_nodes))
+    if bad & L.NBRBLOCK_BAD_REPEAT:
+        raise ValueError("sample_blocks: seeds must not repeat")
+
+    blocks = []
+    for h in range(n_hops):
+        _check_total(total + n_known)
+        out_col, out_w = _launch_sample(sampler, st, node_list, n_known, out_ptr, total, padding, hop_seeds[h], flag)
+        grown = torch.zeros(n_known + total, dtype=torch.int32, device=dev)      # room for every sampled id to be new
+        grown[:n_known] = node_list[:n_known]
+        vcol = torch.empty(total, dtype=torch.int32, device=dev)
+        n_new_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        if total > 0:
+            ws_bytes = lib.tfgx_nbrblock_relabel_workspace_bytes(total)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            L.check(lib.tfgx_nbrblock_relabel(L.ptr(st.table), st.n_nodes, n_known, L.ptr(out_col), total, L.ptr(vcol),
+                                              L.ptr(grown), L.ptr(n_new_dev), L.ptr(ws), ws_bytes, stream),
+                    "tfgx_nbrblock_relabel")
+        if h + 1 < n_hops:
+            # the next hop's counts over the whole buffer (entries past the new total are masked out), so that ONE host read
+            # brings both the new-node total and the next hop's edge total
+            live = torch.arange(n_known + total, device=dev) < (n_known + n_new_dev[0])
+            deg = torch.where(live, _degrees(st, grown), torch.zeros_like(grown))
+            next_cnt = _counts(deg, int(fanouts[n_hops - 2 - h]), None, padding)
+            next_ptr, next_total_dev = _out_ptr(next_cnt)
+            n_new, next_total = torch.stack([n_new_dev[0].long(), next_total_dev]).tolist()
+        else:
+            n_new, bad = torch.stack([n_new_dev[0].long(), flag[0].long()]).tolist()
+            if bad:
+                raise L.TfgxError("sample_blocks: the sampler refused a row id it produced itself")
+        syncs += 1
+        n_src = n_known + n_new
+        ei = torch.stack([_row_positions(cnt, n_known, total), vcol])
+        # the kernels have written the list: hand its plan on with it (out_ptr IS the row_ptr; no sort)
+        attach_plan(ei, CsrPlan.from_sorted(out_ptr, vcol, n_src, edge_index=ei))
+        blocks.append(SampledBlock(ei, out_w.contiguous(), n_known, n_src))
+        node_list, n_known = grown, n_src
+        if h + 1 < n_hops:
+            cnt, out_ptr, total = next_cnt[:n_src].contiguous(), next_ptr[:n_src + 1].contiguous(), next_total
+
+    L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node_list), n_known, stream), "tfgx_nbrblock_reset")
+    st.dirty = False
+    return SampledMinibatch(blocks[::-1], node_list[:n_known].contiguous(), num_seeds, hop_seeds, syncs)
