@@ -10,52 +10,21 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "tfgx.h")
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_library_exports_every_declared_symbol():
+    """tfgx.h, by name (tests/test_abi_registry.py holds every header to its table type by type)."""
     from tf_geometric_amd import _lib
-    lib = _lib.load_library()
-    names = _declared_functions()
-    assert len(names) >= 19
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-    assert set(names) == set(_lib.SIGNATURES), "ctypes table and header disagree: {}".format(
-        set(names) ^ set(_lib.SIGNATURES))
-    assert lib.tfgx_version() == 114          # include/tfgx.h TFGX_ABI_VERSION == _lib.ABI_VERSION
+    assert set(abi_header.declarations("tfgx.h")) == set(_lib.SIGNATURES) <= abi_header.exported_symbols()
 
 
 def test_structs_match_header_layout(tmp_path):
-    """Compile a tiny C program against include/tfgx.h and compare sizeof/offsetof with the ctypes mirrors."""
+    """sizeof / offsetof of the two launch structs through gcc against the ctypes mirrors."""
     from tf_geometric_amd import _lib
-    src = tmp_path / "layout.c"
-    fields_r = [f for f, _ in _lib.ReduceArgs._fields_]
-    fields_g = [f for f, _ in _lib.GatArgs._fields_]
-    body = ['#include <stdio.h>', '#include <stddef.h>', '#include "tfgx.h"', 'int main(void){',
-            'printf("%zu\\n", sizeof(tfgx_reduce_args));']
-    body += ['printf("%zu\\n", offsetof(tfgx_reduce_args, {}));'.format(f) for f in fields_r]
-    body += ['printf("%zu\\n", sizeof(tfgx_gat_args));']
-    body += ['printf("%zu\\n", offsetof(tfgx_gat_args, {}));'.format(f) for f in fields_g]
-    body += ['return 0;}']
-    src.write_text("\n".join(body))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals[0] == ctypes.sizeof(_lib.ReduceArgs)
-    for f, off in zip(fields_r, vals[1:1 + len(fields_r)]):
-        assert getattr(_lib.ReduceArgs, f).offset == off, f
-    rest = vals[1 + len(fields_r):]
-    assert rest[0] == ctypes.sizeof(_lib.GatArgs)
-    for f, off in zip(fields_g, rest[1:]):
-        assert getattr(_lib.GatArgs, f).offset == off, f
+    for c_struct in ("tfgx_reduce_args", "tfgx_gat_args"):
+        abi_header.struct_layout("tfgx.h", c_struct, _lib.STRUCTS[c_struct], tmp_path)
 
 
 def test_argument_validation_without_gpu():

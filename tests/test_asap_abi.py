@@ -1,38 +1,14 @@
 # coding=utf-8
-"""include/tfgx_asap.h (ASAP pooling: the fused attention and the sparse S^T A S) without a GPU: the header compiles as C and
-as C++, every declared symbol is exported and bound by its own ctypes table with the declared argument types (tfgx.h and its
-version untouched), the version function returns the macro, the host argument checks name the refused member before any
-device work — the oversized expansion among them — and zero sizes succeed."""
+"""include/tfgx_asap.h (ASAP pooling: the fused attention and the sparse S^T A S) without a GPU: the exact list of its names and
+its own macro (the uniform header / table / version checks are tests/test_abi_registry.py's), the host argument checks name the
+refused member before any device work — the oversized expansion among them — and zero sizes succeed."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
+from abi_header import declarations, macro, refused as _refused
 
-HEADER = os.path.join(ROOT, "include", "tfgx_asap.h")
-
-CTYPE_OF = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32,
-            "float": ctypes.c_float, "uint64_t": ctypes.c_uint64, "tfgx_stream_t": ctypes.c_void_p}
-
-
-def _declarations():
-    """name -> (return ctype, [argument ctypes]) parsed from the header (any pointer but int64_t* is a void pointer in the
-    tables of _lib.py; the host int64_t* of tfgx_spasp_count is bound as POINTER(c_int64) when it is an output to the host)."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(tfgx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
-        types = []
-        for a in [a.strip() for a in args.split(",") if a.strip() and a.strip() != "void"]:
-            if "*" in a:
-                host_total = name == "tfgx_spasp_count" and re.search(r"\btotal$", a)
-                types.append(ctypes.POINTER(ctypes.c_int64) if host_total else ctypes.c_void_p)
-            else:
-                types.append(CTYPE_OF[a.replace("const", "").split()[0]])
-        out[name] = (CTYPE_OF[ret], types)
-    return out
+HEADER = "tfgx_asap.h"
 
 
 def _lib():
@@ -40,32 +16,14 @@ def _lib():
     return _lib.load_library()
 
 
-@pytest.mark.parametrize("compiler, lang", [("gcc", "c"), ("g++", "c++")])
-def test_header_compiles_as_c_and_cxx(compiler, lang, tmp_path):
-    src = tmp_path / ("t." + ("c" if lang == "c" else "cc"))
-    src.write_text('#include "tfgx_asap.h"\nint main(void) { return TFGX_ASAP_ABI_VERSION == 1 && TFGX_ASAP_MAX_FEATURES > 0 ? 0 : 1; }\n')
-    subprocess.check_call([compiler, "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
-
-
 def test_symbols_versions_and_signatures():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    decl = _declarations()
-    assert sorted(decl) == ["tfgx_asap_attend_backward_f32", "tfgx_asap_attend_f32", "tfgx_asap_version", "tfgx_spasp_count",
-                            "tfgx_spasp_count_workspace_bytes", "tfgx_spasp_emit", "tfgx_spasp_reduce",
-                            "tfgx_spasp_workspace_bytes"]
-    assert set(decl) == set(L.ASAP_SIGNATURES)
-    for name, (res, args) in decl.items():
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        bound_res, bound_args = L.ASAP_SIGNATURES[name]
-        assert bound_res is res, name
-        assert list(bound_args) == args, "{}: _lib.py binds {} but the header declares {}".format(name, bound_args, args)
-        assert getattr(lib, name).argtypes == bound_args
-    src = open(HEADER).read()
-    assert lib.tfgx_asap_version() == L.ASAP_ABI_VERSION == int(re.search(r"#define\s+TFGX_ASAP_ABI_VERSION\s+(\d+)", src).group(1))
-    assert L.ASAP_MAX_FEATURES == int(re.search(r"#define\s+TFGX_ASAP_MAX_FEATURES\s+(\d+)", src).group(1))
-    assert lib.tfgx_version() == L.ABI_VERSION == 114          # tfgx.h did not move
-    assert re.search(r"#define\s+TFGX_ABI_VERSION\s+114\b", open(os.path.join(ROOT, "include", "tfgx.h")).read())
+    assert sorted(declarations(HEADER)) == sorted(L.ASAP_SIGNATURES) == [
+        "tfgx_asap_attend_backward_f32", "tfgx_asap_attend_f32", "tfgx_asap_version", "tfgx_spasp_count",
+        "tfgx_spasp_count_workspace_bytes", "tfgx_spasp_emit", "tfgx_spasp_reduce", "tfgx_spasp_workspace_bytes"]
+    assert L.ASAP_MAX_FEATURES == macro(HEADER, "TFGX_ASAP_MAX_FEATURES") > 0
+    # the host int64_t* of tfgx_spasp_count is an output to the host: bound with its type
+    assert L.ASAP_SIGNATURES["tfgx_spasp_count"][1][9] is ctypes.POINTER(ctypes.c_int64)
 
 
 ATT_OK = dict(row_ptr=8, col=8, N=4, E=6, x=8, ldx=16, F=16, sq=8, sh=8, bias=8, drop_rate=0.0, seed=0, c=8, ldc=16, p=8,
@@ -76,15 +34,6 @@ EMIT_OK = dict(s_row_ptr=8, s_col=8, s_val=None, N=4, K=2, a_row=8, a_col=8, a_v
                ws=8, ws_bytes=1 << 30, stream=None)
 REDUCE_OK = dict(total=10, K=2, drop_diagonal=0, out_row=8, out_col=8, out_val=8, out_row_ptr=8, out_count=8, ws=8,
                  ws_bytes=1 << 30, stream=None)
-
-
-def _refused(fn, ok, change, word, code=1):
-    """Every refusal happens on the host, before any device work (the pointers here are never dereferenced)."""
-    lib = _lib()
-    rc = getattr(lib, fn)(*dict(ok, **change).values())
-    assert rc == code, rc
-    msg = lib.tfgx_last_error().decode()
-    assert word in msg and fn in msg, msg
 
 
 @pytest.mark.parametrize("change, word", [

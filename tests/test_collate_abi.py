@@ -1,29 +1,18 @@
 # coding=utf-8
-"""include/tfgx_collate.h (minibatch assembly out of a packed device dataset) without a GPU: every declared symbol is exported
-and bound by its own ctypes table (outside _lib.SIGNATURES; tfgx.h and its version are untouched), the struct members are the
-ctypes fields in order, every refusal happens on the host with the member named, the zero-size calls succeed; the numpy mirror
+"""include/tfgx_collate.h (minibatch assembly out of a packed device dataset) without a GPU: the exact list of its names, which
+no other header's table and not tfgx.h know (the uniform header / table / version / struct checks are
+tests/test_abi_registry.py's), the tile the data module uses, every refusal happens on the host with the member named, the zero-size calls succeed; the numpy mirror
 of the whole operator (outputs and the three plans; the exact reference of tests/test_gpu_collate.py) keeps its promises; and
 the host side of tfg.data.GraphStore — refusals that name the graph, IndexError, the batch table's ptr arithmetic."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_header import declarations, macro, source
 from test_drop_edge_abi import mirror_plan
 
-HEADER = os.path.join(ROOT, "include", "tfgx_collate.h")
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _struct_members(name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), _header(), flags=re.S).group(1)
-    return re.findall(r"([A-Za-z_][A-Za-z_0-9]*)\s*;", body)
+HEADER = "tfgx_collate.h"
 
 
 # ---- the mirror: test infrastructure shared with the GPU tests ----------------------------------------------------------
@@ -72,32 +61,12 @@ def random_dataset(rng, sizes, F, y=True):
 # ---- ABI ----------------------------------------------------------------------------------------------------------------
 def test_collate_symbols_versions_and_struct_layout():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", _header())))
-    assert names == ["tfgx_collate", "tfgx_collate_tile", "tfgx_collate_version"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-    assert set(names) == set(L.COLLATE_SIGNATURES)
-    assert lib.tfgx_collate_version() == L.COLLATE_ABI_VERSION == 1
-    assert lib.tfgx_version() == 114 and L.ABI_VERSION == 114
-    tables = [L.SIGNATURES, L.H16_SIGNATURES, L.FUSED_H16_SIGNATURES, L.GEMM_H16_SIGNATURES, L.DROPEDGE_SIGNATURES,
-              L.LINKPRED_SIGNATURES, L.LSTM_SIGNATURES, L.SET2SET_SIGNATURES, L.ASAP_SIGNATURES, L.SEGGRAM_SIGNATURES,
-              L.NORMGRAD_SIGNATURES]
-    for t in tables:
-        assert not set(L.COLLATE_SIGNATURES) & set(t)
-        assert not any("collate" in n for n in t)
-    tfgx_h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tfgx.h")).read(), flags=re.S)
-    assert "collate" not in tfgx_h
-    hdr = open(HEADER).read()
-    assert re.search(r"#define\s+TFGX_COLLATE_ABI_VERSION\s+1\b", hdr)
-    tile = int(re.search(r"#define\s+TFGX_COLLATE_TILE\s+(\d+)\b", hdr).group(1))
+    assert sorted(declarations(HEADER)) == sorted(L.COLLATE_SIGNATURES) == ["tfgx_collate", "tfgx_collate_tile", "tfgx_collate_version"]
+    for abi in L.ABIS:
+        assert abi.signatures is L.COLLATE_SIGNATURES or not any("collate" in n for n in abi.signatures), abi.header
+    assert "collate" not in source("tfgx.h")
     from tf_geometric_amd import data
-    assert lib.tfgx_collate_tile() == tile == L.COLLATE_TILE == data.COLLATE_TILE
-    assert _struct_members("tfgx_collate_plan") == [f[0] for f in L.CollatePlan._fields_]
-    assert ctypes.sizeof(L.CollatePlan) == 6 * ctypes.sizeof(ctypes.c_void_p)
-    assert _struct_members("tfgx_collate_args") == [f[0] for f in L.CollateArgs._fields_]
-    assert ctypes.sizeof(L.CollateArgs) == 21 * 8          # 21 members, each a pointer or an int64
+    assert L.load_library().tfgx_collate_tile() == macro(HEADER, "TFGX_COLLATE_TILE") == L.COLLATE_TILE == data.COLLATE_TILE
 
 
 FAKE = dict(ds_x=1 << 30, ds_ldx=8, F=8, ds_row=2 << 30, ds_col=3 << 30, ds_w=4 << 30, ds_n=100, ds_e=300, table=5 << 30, B=4,

@@ -1,26 +1,18 @@
 # coding=utf-8
-"""include/tfgx_dropedge.h (DropEdge) without a GPU: every declared symbol is exported and bound by its own ctypes table
-(outside _lib.SIGNATURES; tfgx.h and its version are untouched), the host argument checks name the refused member before
+"""include/tfgx_dropedge.h (DropEdge) without a GPU: the exact list of its names, of which tfgx.h knows none (the uniform header /
+table / version / struct checks are tests/test_abi_registry.py's), the host argument checks name the refused member before
 any device work, E = 0 succeeds, the numpy mirror of the whole operator (both forms, attributes included; used as the exact
 reference by tests/test_gpu_drop_edge.py) keeps its promises, the keep rule's kept fraction sits inside the binomial's
 5 sigma, and the Python entry points return their inputs when not training."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from abi_header import declarations, source
 
-HEADER = os.path.join(ROOT, "include", "tfgx_dropedge.h")
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
+HEADER = "tfgx_dropedge.h"
 
 
 def _lib():
@@ -68,27 +60,12 @@ def _random_edges(rng, n_dst, n_src, e):
 # ---- ABI -------------------------------------------------------------------------------------------------------------------
 def test_dropedge_symbols_and_versions():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_drop_edge_count", "tfgx_drop_edge_emit", "tfgx_drop_edge_workspace_bytes", "tfgx_dropedge_version"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-    assert set(names) == set(L.DROPEDGE_SIGNATURES), set(names) ^ set(L.DROPEDGE_SIGNATURES)
-    assert lib.tfgx_dropedge_version() == L.DROPEDGE_ABI_VERSION == 1
-    assert lib.tfgx_version() == 114 and L.ABI_VERSION == 114
-    assert not set(L.DROPEDGE_SIGNATURES) & set(L.SIGNATURES)
+    assert sorted(declarations(HEADER)) == sorted(L.DROPEDGE_SIGNATURES) == [
+        "tfgx_drop_edge_count", "tfgx_drop_edge_emit", "tfgx_drop_edge_workspace_bytes", "tfgx_dropedge_version"]
     assert not any("drop_edge" in n or "dropedge" in n for n in L.SIGNATURES)
-    tfgx_h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tfgx.h")).read(), flags=re.S)
-    assert "drop_edge" not in tfgx_h and "dropedge" not in tfgx_h
-    hdr = open(HEADER).read()
-    assert re.search(r"#define\s+TFGX_DROPEDGE_ABI_VERSION\s+1\b", hdr)
-    # struct tfgx_drop_edge_plan: six pointers, in the header's order
-    body = re.search(r"typedef struct tfgx_drop_edge_plan \{(.*?)\} tfgx_drop_edge_plan;", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S),
-                     flags=re.S).group(1)
-    members = re.findall(r"\*\s*([a-z_]+)\s*;", body)
-    assert members == [f[0] for f in L.DropEdgePlan._fields_]
-    assert ctypes.sizeof(L.DropEdgePlan) == 6 * ctypes.sizeof(ctypes.c_void_p)
+    assert "drop_edge" not in source("tfgx.h") and "dropedge" not in source("tfgx.h")
+    # struct tfgx_drop_edge_plan: six pointers
+    assert [t for _, t in L.DropEdgePlan._fields_] == [ctypes.c_void_p] * 6
 
 
 def _count(lib, row=1 << 30, col=2 << 30, E=10, n_dst=5, n_src=5, rate=0.5, seed=1, und=0, n_out=True, ws=3 << 30, ws_bytes=1 << 20):

@@ -1,6 +1,6 @@
 # coding=utf-8
-"""include/tfgx_fused_h16.h (the fused aggregate -> project launch over a 16-bit table) without a GPU: the declared symbols
-are exported and bound by their own ctypes table, the three tables stay disjoint, every refusal names its member before any
+"""include/tfgx_fused_h16.h (the fused aggregate -> project launch over a 16-bit table) without a GPU: the exact list of its
+names (the uniform header / table / version checks are tests/test_abi_registry.py's), every refusal names its member before any
 device work (launch and describe), describe names the instantiation the dispatch mirror predicts, and the draws of
 tests/test_gpu_fused_h16.py reach every (DT, G, WEIGHTED) instantiation with resident and streamed B, hub and non-hub plans."""
 import ctypes
@@ -9,11 +9,11 @@ import re
 
 import numpy as np
 
-from conftest import ROOT
+from abi_header import declarations
 from test_gpu_fuzz_backward import _graph, _rng
 from test_h16_abi import BF16, F16, _rmat, _roundup8
 
-HEADER = os.path.join(ROOT, "include", "tfgx_fused_h16.h")
+HEADER = "tfgx_fused_h16.h"
 _SCALE = int(os.environ.get("TFGX_FUZZ_SCALE", "1"))
 
 # the issue's lists: tile edges; the G switch (F <= 64 -> 8 lanes, F % 8 == 4 leaves a half-valid last lane); job counts
@@ -80,24 +80,11 @@ def draw_fused_h16(seed):
     return d
 
 
-def _declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_fused_h16_symbols_and_versions():
     from tf_geometric_amd import _lib
-    lib = _lib.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_aggregate_gemm_h16", "tfgx_aggregate_gemm_h16_describe", "tfgx_fused_h16_version"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-    assert set(names) == set(_lib.FUSED_H16_SIGNATURES)
-    assert lib.tfgx_fused_h16_version() == _lib.FUSED_H16_ABI_VERSION == 1
-    assert re.search(r"#define TFGX_FUSED_H16_ABI_VERSION 1\b", open(HEADER).read())
-    tables = [set(_lib.SIGNATURES), set(_lib.H16_SIGNATURES), set(_lib.FUSED_H16_SIGNATURES)]
-    assert not (tables[0] & tables[1]) and not (tables[0] & tables[2]) and not (tables[1] & tables[2])
-    assert lib.tfgx_version() == 114 and lib.tfgx_h16_version() == 1
+    names = sorted(declarations(HEADER))
+    assert names == sorted(_lib.FUSED_H16_SIGNATURES) == [
+        "tfgx_aggregate_gemm_h16", "tfgx_aggregate_gemm_h16_describe", "tfgx_fused_h16_version"]
     # the envelope is the float32 launch's, reused and not redeclared
     assert "tfgx_aggregate_gemm_fits" not in names and "tfgx_aggregate_gemm_fits" in _lib.SIGNATURES
 

@@ -1,7 +1,7 @@
 # coding=utf-8
 """include/tfgx_gemm_h16.h (the dense GEMM and its weight gradient reading a 16-bit table) without a GPU: every declared symbol
-is exported and bound by its own ctypes table, the other headers' tables and versions are untouched, every refusal names its
-member before any device work (launch and describe), describe honours its buffer, and for every shape of the route table
+pinned by the exact list of its names (the uniform header / table / version checks are tests/test_abi_registry.py's), every
+refusal names its member before any device work (launch and describe), describe honours its buffer, and for every shape of the route table
 (and a seeded sweep of random shapes) the 16-bit call on a table of either stride takes the route of the float32 call on the
 dense widened matrix: tfgx_gemm_h16_describe == dtype tag + tfgx_gemm_describe(lda = K)."""
 import ctypes
@@ -12,9 +12,10 @@ import sys
 
 import numpy as np
 
+from abi_header import declarations
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "tfgx_gemm_h16.h")
+HEADER = "tfgx_gemm_h16.h"
 BF16, F16 = 1, 2
 TAG = {BF16: "bf16 ", F16: "f16 "}
 A_PTR, B_PTR, C_PTR, WS_PTR = 1 << 30, 2 << 30, 3 << 30, 4 << 30      # 16-byte aligned; describe never dereferences them
@@ -60,11 +61,6 @@ def roundup8(k):
     return (k + 7) // 8 * 8
 
 
-def _declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
-
-
 def f32_route(lib, M, K, N, lent, a=A_PTR, b=B_PTR, c=C_PTR, ldb=None, ldc=None, ws=WS_PTR):
     """tfgx_gemm_describe for a dense float32 A (lda = K)."""
     buf = ctypes.create_string_buffer(200)
@@ -84,24 +80,10 @@ def h16_route(lib, dt, lda, M, K, N, lent, a=A_PTR, b=B_PTR, c=C_PTR, ldb=None, 
 
 def test_gemm_h16_symbols_and_versions():
     from tf_geometric_amd import _lib
-    lib = _lib.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_gemm_bias_act_cols_ws_h16", "tfgx_gemm_h16_describe", "tfgx_gemm_h16_version", "tfgx_gemm_tn_gated_h16"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-    assert set(names) == set(_lib.GEMM_H16_SIGNATURES)
-    assert lib.tfgx_gemm_h16_version() == _lib.GEMM_H16_ABI_VERSION == 1
-    assert re.search(r"#define TFGX_GEMM_H16_ABI_VERSION 1\b", open(HEADER).read())
-    assert lib.tfgx_version() == 114 and lib.tfgx_h16_version() == 1 and lib.tfgx_fused_h16_version() == 1
-    others = [_lib.SIGNATURES, _lib.H16_SIGNATURES, _lib.FUSED_H16_SIGNATURES]
-    for t in others:
-        assert not set(t) & set(_lib.GEMM_H16_SIGNATURES)
+    names = sorted(declarations(HEADER))
+    assert names == sorted(_lib.GEMM_H16_SIGNATURES) == [
+        "tfgx_gemm_bias_act_cols_ws_h16", "tfgx_gemm_h16_describe", "tfgx_gemm_h16_version", "tfgx_gemm_tn_gated_h16"]
     assert not any("h16" in n for n in _lib.SIGNATURES)
-    # argument counts against the header's declarations
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name, params in re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(([^)]*)\)", src):
-        count = 0 if params.strip() == "void" else params.count(",") + 1
-        assert count == len(_lib.GEMM_H16_SIGNATURES[name][1]), name
     # the workspace sizes are the float32 entries': no new size function
     assert not [n for n in names if "workspace" in n]
 

@@ -1,6 +1,6 @@
 # coding=utf-8
-"""include/tfgx_linkpred.h (link prediction) without a GPU: every declared symbol is exported and bound by its own ctypes
-table (tfgx.h and its version untouched), the host argument checks name the refused member before any device work, zero
+"""include/tfgx_linkpred.h (link prediction) without a GPU: the exact list of its names, of which tfgx.h knows none (the uniform
+header / table / version checks are tests/test_abi_registry.py's), the host argument checks name the refused member before any device work, zero
 sizes succeed, and the numpy mirror of both samplers — built ONLY on tfgx_negative_draw called from the host, used as the
 exact reference by tests/test_gpu_linkpred.py — is uniform over the non-edges within the binomial's 5 sigma.  The torch-op
 utilities (extract_unique_edge, the hash converters) are compared with the reference's own outputs
@@ -14,21 +14,16 @@ import numpy as np
 import pytest
 import torch
 
+from abi_header import declarations, source
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "tfgx_linkpred.h")
+HEADER = "tfgx_linkpred.h"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "link_cases.npz")
 
 # the fixed graph of the uniformity checks: 8 nodes, 10 undirected edges -> 28 - 10 = 18 non-edges; no node is full
 GRAPH8 = np.array([[0, 0, 0, 1, 1, 2, 3, 4, 5, 6],
                    [1, 2, 3, 2, 4, 5, 6, 7, 6, 7]], dtype=np.int32)
 N8 = 8
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
 
 
 def _lib():
@@ -119,28 +114,13 @@ def within_five_sigma(counts, trials, p):
 # ---- ABI -------------------------------------------------------------------------------------------------------------------
 def test_linkpred_symbols_and_versions():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_edge_dot_f32", "tfgx_linkpred_version", "tfgx_negative_draw", "tfgx_negative_sample_from",
-                     "tfgx_negative_sample_pairs"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-    assert set(names) == set(L.LINKPRED_SIGNATURES), set(names) ^ set(L.LINKPRED_SIGNATURES)
-    assert lib.tfgx_linkpred_version() == L.LINKPRED_ABI_VERSION == 1
-    assert lib.tfgx_version() == 114 and L.ABI_VERSION == 114
-    assert not set(L.LINKPRED_SIGNATURES) & set(L.SIGNATURES)
-    tfgx_h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tfgx.h")).read(), flags=re.S)
+    assert sorted(declarations(HEADER)) == sorted(L.LINKPRED_SIGNATURES) == [
+        "tfgx_edge_dot_f32", "tfgx_linkpred_version", "tfgx_negative_draw", "tfgx_negative_sample_from",
+        "tfgx_negative_sample_pairs"]
+    tfgx_h = source("tfgx.h")
     assert "edge_dot" not in tfgx_h and "negative_" not in tfgx_h and "linkpred" not in tfgx_h
-    hdr = open(HEADER).read()
-    assert re.search(r"#define\s+TFGX_LINKPRED_ABI_VERSION\s+1\b", hdr)
-    assert L.NEGATIVE_BAD_START == -(1 << 31) and re.search(r"#define\s+TFGX_NEGATIVE_BAD_START\s+\(\(int32_t\)0x80000000\)", hdr)
-    # the number of parameters of every declaration equals the bound table's
-    flat = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in names:
-        params = re.search(r"\b{}\s*\((.*?)\)\s*;".format(name), flat, flags=re.S).group(1).strip()
-        count = 0 if params == "void" else len(params.split(","))
-        assert count == len(L.LINKPRED_SIGNATURES[name][1]), name
+    assert L.NEGATIVE_BAD_START == -(1 << 31)
+    assert re.search(r"#define\s+TFGX_NEGATIVE_BAD_START\s+\(\(int32_t\)0x80000000\)", source(HEADER))
 
 
 P = [k << 30 for k in range(1, 9)]      # distinct non-null stand-ins: a refused call never touches them

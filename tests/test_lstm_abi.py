@@ -1,6 +1,6 @@
 # coding=utf-8
-"""include/tfgx_lstm.h (the LSTM GraphSAGE aggregator) without a GPU: every declared symbol is exported and bound by its own
-ctypes table (tfgx.h and its version untouched), the host argument checks name the refused member before any device work,
+"""include/tfgx_lstm.h (the LSTM GraphSAGE aggregator) without a GPU: the exact list of its names (the uniform header /
+table / version checks are tests/test_abi_registry.py's), the host argument checks name the refused member before any device work,
 zero sizes succeed, and the float64 torch mirror of the layer (tests/lstm_mirror.py, the exact reference of
 tests/test_gpu_lstm_sage.py) reproduces every case the reference's own lstm_graph_sage wrote into
 tests/golden/lstm_sage_cases.npz (tests/golden/make_lstm_sage_golden.py) to 1e-12; torch.nn.LSTM cross-checks the recurrence."""
@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from abi_header import declarations, source
 from conftest import ROOT
 import lstm_mirror as M
 
-HEADER = os.path.join(ROOT, "include", "tfgx_lstm.h")
+HEADER = "tfgx_lstm.h"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "lstm_sage_cases.npz")
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
 
 
 def _lib():
@@ -49,18 +44,9 @@ def mirror_of_case(c, dtype=torch.float64):
 
 def test_lstm_symbols_and_versions():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_lstm_aggregate_backward_f32", "tfgx_lstm_aggregate_f32", "tfgx_lstm_aggregate_saved_bytes",
-                     "tfgx_lstm_aggregate_tiles", "tfgx_lstm_recurrent_kernel_resident", "tfgx_lstm_version"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-    assert set(names) == set(L.LSTM_SIGNATURES), set(names) ^ set(L.LSTM_SIGNATURES)
-    assert lib.tfgx_lstm_version() == L.LSTM_ABI_VERSION == 1
-    assert re.search(r"#define\s+TFGX_LSTM_ABI_VERSION\s+1\b", open(HEADER).read())
-    assert lib.tfgx_version() == L.ABI_VERSION == 114
-    assert re.search(r"#define\s+TFGX_ABI_VERSION\s+114\b", open(os.path.join(ROOT, "include", "tfgx.h")).read())
+    assert sorted(declarations(HEADER)) == sorted(L.LSTM_SIGNATURES) == [
+        "tfgx_lstm_aggregate_backward_f32", "tfgx_lstm_aggregate_f32", "tfgx_lstm_aggregate_saved_bytes",
+        "tfgx_lstm_aggregate_tiles", "tfgx_lstm_recurrent_kernel_resident", "tfgx_lstm_version"]
 
 
 def test_lstm_size_queries():
@@ -114,7 +100,7 @@ def test_backward_argument_checks_name_the_member(change, word):
 
 
 def test_invalid_arg_code_is_one():
-    assert re.search(r"TFGX_ERR_INVALID_ARG\s*=?\s*1\b", open(os.path.join(ROOT, "include", "tfgx.h")).read())
+    assert re.search(r"TFGX_ERR_INVALID_ARG\s*=?\s*1\b", source("tfgx.h"))
 
 
 @pytest.mark.parametrize("change", [dict(n_dst=0), dict(U=0, ldp=0, ldo=0)])

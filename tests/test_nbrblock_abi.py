@@ -1,24 +1,19 @@
 # coding=utf-8
-"""include/tfgx_nbrblock.h (minibatch neighbour sampling) without a GPU: every declared symbol is exported and bound by its own
-ctypes table (outside every other table; tfgx.h and its version are untouched), every refusal happens on the host with the
+"""include/tfgx_nbrblock.h (minibatch neighbour sampling) without a GPU: the exact list of its names, which no other header's
+table and not tfgx.h know (the uniform header / table / version checks are tests/test_abi_registry.py's), every refusal happens on the host with the
 argument named, the zero-size calls succeed; the numpy mirror of the relabel and block assembly (the exact reference of
 tests/test_gpu_nbrblock.py) is held to np.unique(..., return_index=True) on hand-written cases; and the Python-side refusals of
 RandomNeighborSampler.sample_rows / sample_blocks that need no device."""
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_header import INCLUDE, declarations, macro, refused as _refused
 
-HEADER = os.path.join(ROOT, "include", "tfgx_nbrblock.h")
+HEADER = "tfgx_nbrblock.h"
 NAMES = ["tfgx_nbrblock_relabel", "tfgx_nbrblock_relabel_workspace_bytes", "tfgx_nbrblock_reset", "tfgx_nbrblock_sample_rows",
          "tfgx_nbrblock_stamp", "tfgx_nbrblock_version"]
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 # ---- the mirror: test infrastructure shared with the GPU tests ----------------------------------------------------------
@@ -66,41 +61,14 @@ def lists_of(edge_index, edge_weight):
 # ---- ABI ----------------------------------------------------------------------------------------------------------------
 def test_nbrblock_symbols_and_versions():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", _header())))
-    assert names == NAMES
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-        assert list(getattr(lib, name).argtypes) == L.NBRBLOCK_SIGNATURES[name][1]
-    assert set(names) == set(L.NBRBLOCK_SIGNATURES)
-    assert all(n.startswith("tfgx_nbrblock_") for n in L.NBRBLOCK_SIGNATURES)
-    hdr = open(HEADER).read()
-    assert re.search(r"#define\s+TFGX_NBRBLOCK_ABI_VERSION\s+1\b", hdr)
-    assert lib.tfgx_nbrblock_version() == L.NBRBLOCK_ABI_VERSION == 1
-    assert int(re.search(r"#define\s+TFGX_NBRBLOCK_EMPTY\s+(\d+)\b", hdr).group(1)) == L.NBRBLOCK_EMPTY == 2 ** 31 - 1
-    assert int(re.search(r"#define\s+TFGX_NBRBLOCK_BAD_RANGE\s+(\d+)\b", hdr).group(1)) == L.NBRBLOCK_BAD_RANGE
-    assert int(re.search(r"#define\s+TFGX_NBRBLOCK_BAD_REPEAT\s+(\d+)\b", hdr).group(1)) == L.NBRBLOCK_BAD_REPEAT
-    assert lib.tfgx_version() == 114 and L.ABI_VERSION == 114
-    tables = [L.SIGNATURES, L.H16_SIGNATURES, L.FUSED_H16_SIGNATURES, L.GEMM_H16_SIGNATURES, L.DROPEDGE_SIGNATURES,
-              L.LINKPRED_SIGNATURES, L.LSTM_SIGNATURES, L.SET2SET_SIGNATURES, L.ASAP_SIGNATURES, L.SEGGRAM_SIGNATURES,
-              L.NORMGRAD_SIGNATURES, L.COLLATE_SIGNATURES]
-    for t in tables:
-        assert not set(L.NBRBLOCK_SIGNATURES) & set(t)
-        assert not any("nbrblock" in n for n in t)
-    tfgx_h = open(os.path.join(ROOT, "include", "tfgx.h")).read()
-    assert "nbrblock" not in tfgx_h
-    assert re.search(r"#define\s+TFGX_ABI_VERSION\s+114\b", tfgx_h)
-
-
-def test_the_header_argument_counts_are_the_bound_ones():
-    """Each declaration's parameter list has as many entries as its ctypes row."""
-    from tf_geometric_amd import _lib as L
-    hdr = _header()
-    for name in NAMES:
-        params = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, hdr, flags=re.S).group(1).strip()
-        n = 0 if params == "void" else len(params.split(","))
-        assert n == len(L.NBRBLOCK_SIGNATURES[name][1]), name
+    assert sorted(declarations(HEADER)) == sorted(L.NBRBLOCK_SIGNATURES) == NAMES
+    assert all(n.startswith("tfgx_nbrblock_") for n in NAMES)
+    assert macro(HEADER, "TFGX_NBRBLOCK_EMPTY") == L.NBRBLOCK_EMPTY == 2 ** 31 - 1
+    assert macro(HEADER, "TFGX_NBRBLOCK_BAD_RANGE") == L.NBRBLOCK_BAD_RANGE
+    assert macro(HEADER, "TFGX_NBRBLOCK_BAD_REPEAT") == L.NBRBLOCK_BAD_REPEAT
+    for abi in L.ABIS:
+        assert abi.signatures is L.NBRBLOCK_SIGNATURES or not any("nbrblock" in n for n in abi.signatures), abi.header
+    assert "nbrblock" not in open(os.path.join(INCLUDE, "tfgx.h")).read()          # not even in a comment
 
 
 P = [(i + 1) << 30 for i in range(12)]        # fake device pointers: never dereferenced on the host
@@ -111,15 +79,6 @@ RELABEL_OK = dict(table=P[0], n_nodes=100, n_known=10, cols=P[1], E=50, out_vcol
                   workspace=P[5], workspace_bytes=1 << 30, stream=None)
 RESET_OK = dict(table=P[0], n_nodes=100, node_list=P[1], n=10, stream=None)
 BIG = 1 << 31
-
-
-def _refused(fn, ok, change, word, code=1):
-    from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    rc = getattr(lib, fn)(*dict(ok, **change).values())
-    assert rc == code, (fn, change, rc)
-    msg = lib.tfgx_last_error().decode()
-    assert word in msg and fn in msg, msg
 
 
 @pytest.mark.parametrize("fn, ok, change, word", [

@@ -5,8 +5,8 @@ ReduceArgs ctypes mirror INTEGRATION.md tells a host to paste has the header's l
 import ctypes
 import os
 import re
-import subprocess
 
+import abi_header
 from conftest import ROOT
 
 NEW_SYMBOLS = ["tfgx_hub_policy", "tfgx_gat_source_block_count", "tfgx_plan_row_order_workspace_bytes", "tfgx_plan_row_order",
@@ -21,21 +21,14 @@ def _lib():
     return _lib.load_library()
 
 
-def _header_functions():
-    src = open(os.path.join(ROOT, "include", "tfgx.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src))
-
-
 def test_builders_declared_exported_and_bound():
     from tf_geometric_amd import _lib as L
     lib = _lib()
-    declared = _header_functions()
+    declared = abi_header.declarations("tfgx.h")
     for name in NEW_SYMBOLS:
         assert name in declared, name
         assert hasattr(lib, name), name
         assert name in L.SIGNATURES, name
-    assert lib.tfgx_version() == 114
 
 
 def _py_source_block_count(n_dst, n_src, E, A, W, block_bytes=6 << 20, min_edges=32):
@@ -192,20 +185,9 @@ def _integration_reduce_args():
 def test_integration_reduce_args_mirror_has_the_header_layout(tmp_path):
     from tf_geometric_amd import _lib as L
     mirror = _integration_reduce_args()
-    names = [f for f, _ in mirror._fields_]
-    src = tmp_path / "sz.c"
-    body = ['#include <stdio.h>', '#include <stddef.h>', '#include "tfgx.h"', 'int main(void){',
-            'printf("%zu\\n", sizeof(tfgx_reduce_args));']
-    body += ['printf("%zu\\n", offsetof(tfgx_reduce_args, {}));'.format(f) for f in names]
-    body += ['return 0;}']
-    src.write_text("\n".join(body))
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert ctypes.sizeof(mirror) == vals[0] == ctypes.sizeof(L.ReduceArgs)
-    for f, off in zip(names, vals[1:]):
-        assert getattr(mirror, f).offset == off, f
-    assert names == [f for f, _ in L.ReduceArgs._fields_]
+    abi_header.struct_layout("tfgx.h", "tfgx_reduce_args", mirror, tmp_path)
+    assert ctypes.sizeof(mirror) == ctypes.sizeof(L.ReduceArgs)
+    assert [f for f, _ in mirror._fields_] == [f for f, _ in L.ReduceArgs._fields_]
 
 
 def test_gat_demo_uses_only_the_c_abi():

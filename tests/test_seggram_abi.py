@@ -1,33 +1,12 @@
 # coding=utf-8
 """include/tfgx_seggram.h (the segmented transposed product S_g^T Y_g of DiffPool / MinCutPool and its backward) without a GPU:
-the header compiles as C and as C++, every declared symbol is exported and bound by its own ctypes table with the declared
-argument types (tfgx.h and tfgx_asap.h and their versions untouched), the version and block functions return what _lib
-binds, the host argument checks name the refused member before any device work, and zero sizes succeed."""
-import ctypes
-import os
-import re
-import subprocess
-
+the exact list of its names and its own macros (the uniform header / table / version checks are tests/test_abi_registry.py's),
+the host argument checks name the refused member before any device work, and zero sizes succeed."""
 import pytest
 
-from conftest import ROOT
+from abi_header import declarations, macro, refused as _refused
 
-HEADER = os.path.join(ROOT, "include", "tfgx_seggram.h")
-
-CTYPE_OF = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32,
-            "tfgx_stream_t": ctypes.c_void_p}
-
-
-def _declarations():
-    """name -> (return ctype, [argument ctypes]) parsed from the header (every pointer is a void pointer in _lib.py)."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(tfgx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
-        types = []
-        for a in [a.strip() for a in args.split(",") if a.strip() and a.strip() != "void"]:
-            types.append(ctypes.c_void_p if "*" in a else CTYPE_OF[a.replace("const", "").split()[0]])
-        out[name] = (CTYPE_OF[ret], types)
-    return out
+HEADER = "tfgx_seggram.h"
 
 
 def _lib():
@@ -35,58 +14,18 @@ def _lib():
     return _lib.load_library()
 
 
-@pytest.mark.parametrize("compiler, lang", [("gcc", "c"), ("g++", "c++")])
-def test_header_compiles_as_c_and_cxx(compiler, lang, tmp_path):
-    src = tmp_path / ("t." + ("c" if lang == "c" else "cc"))
-    src.write_text('#include "tfgx_seggram.h"\nint main(void) { return TFGX_SEGGRAM_ABI_VERSION == 1 && TFGX_SEGGRAM_MAX_K == 64 ? 0 : 1; }\n')
-    subprocess.check_call([compiler, "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
-
-
 def test_symbols_versions_and_signatures():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    decl = _declarations()
-    assert sorted(decl) == ["tfgx_seggram_block", "tfgx_seggram_version", "tfgx_segment_gram_backward_f32",
-                            "tfgx_segment_gram_f32", "tfgx_segment_gram_workspace_bytes"]
-    assert set(decl) == set(L.SEGGRAM_SIGNATURES)
-    for name, (res, args) in decl.items():
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        bound_res, bound_args = L.SEGGRAM_SIGNATURES[name]
-        assert bound_res is res, name
-        assert list(bound_args) == args, "{}: _lib.py binds {} but the header declares {}".format(name, bound_args, args)
-        assert getattr(lib, name).argtypes == bound_args
-    src = open(HEADER).read()
-    assert lib.tfgx_seggram_version() == L.SEGGRAM_ABI_VERSION == int(
-        re.search(r"#define\s+TFGX_SEGGRAM_ABI_VERSION\s+(\d+)", src).group(1))
-    assert L.SEGGRAM_MAX_K == int(re.search(r"#define\s+TFGX_SEGGRAM_MAX_K\s+(\d+)", src).group(1)) == 64
-    assert lib.tfgx_seggram_block() == L.SEGGRAM_BLOCK > 0
-    assert lib.tfgx_version() == L.ABI_VERSION == 114 and lib.tfgx_asap_version() == L.ASAP_ABI_VERSION == 1   # did not move
-    assert re.search(r"#define\s+TFGX_ABI_VERSION\s+114\b", open(os.path.join(ROOT, "include", "tfgx.h")).read())
-    assert re.search(r"#define\s+TFGX_ASAP_ABI_VERSION\s+1\b", open(os.path.join(ROOT, "include", "tfgx_asap.h")).read())
-
-
-def test_nothing_undeclared_is_exported():
-    """Every tfgx_seggram* / tfgx_segment_gram* symbol of the library is declared in the header."""
-    from tf_geometric_amd import _lib as L
-    L.load_library()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if re.search(r"\bT tfgx_(seggram|segment_gram)", line)}
-    assert exported == set(_declarations())
+    assert sorted(declarations(HEADER)) == sorted(L.SEGGRAM_SIGNATURES) == [
+        "tfgx_seggram_block", "tfgx_seggram_version", "tfgx_segment_gram_backward_f32", "tfgx_segment_gram_f32",
+        "tfgx_segment_gram_workspace_bytes"]
+    assert L.SEGGRAM_MAX_K == macro(HEADER, "TFGX_SEGGRAM_MAX_K") == 64
 
 
 FWD_OK = dict(seg_ptr=8, seg_node=None, G=3, N=200, S=8, lds=5, K=5, Y=8, ldy=20, W=20, out=8, ldo=20, flag=None, ws=8,
               ws_bytes=1 << 30, stream=None)
 BWD_OK = dict(node_seg=8, N=200, G=3, S=8, lds=5, K=5, Y=8, ldy=20, W=20, dOut=8, ldo=20, dS=8, ldds=5, dY=8, lddy=20,
               flag=None, stream=None)
-
-
-def _refused(fn, ok, change, word, code=1):
-    """Every refusal happens on the host, before any device work (the pointers here are never dereferenced)."""
-    lib = _lib()
-    rc = getattr(lib, fn)(*dict(ok, **change).values())
-    assert rc == code, rc
-    msg = lib.tfgx_last_error().decode()
-    assert word in msg and fn in msg, msg
 
 
 @pytest.mark.parametrize("change, word", [

@@ -1,29 +1,22 @@
 # coding=utf-8
-"""include/tfgx_set2set.h (Set2Set: the attention readout and the sequence LSTM) without a GPU: every declared symbol is
-exported and bound by its own ctypes table (tfgx.h and tfgx_lstm.h and their versions untouched), the host argument checks
+"""include/tfgx_set2set.h (Set2Set: the attention readout and the sequence LSTM) without a GPU: the exact list of its names and
+its own macros (the uniform header / table / version checks are tests/test_abi_registry.py's), the host argument checks
 name the refused member before any device work, zero sizes succeed, the size queries return what the header documents, and
 the float64 torch mirror (tests/set2set_mirror.py, the exact reference of tests/test_gpu_set2set.py) reproduces every case
 the reference's own set2set wrote into tests/golden/set2set_cases.npz (tests/golden/make_set2set_golden.py) to 1e-12;
 torch.nn.LSTM cross-checks the mirror's recurrence with a non-zero initial state."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from abi_header import declarations, macro, refused as _refused
 import set2set_mirror as M
-
-HEADER = os.path.join(ROOT, "include", "tfgx_set2set.h")
 from set2set_mirror import GOLDEN, golden_cases, mirror_of_case
 from tf_geometric_amd._lib import SET2SET_CHUNK_ROWS as CHUNK
 
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tfgx_[a-z0-9_]+)\s*\(", src)))
+HEADER = "tfgx_set2set.h"
 
 
 def _lib():
@@ -33,24 +26,12 @@ def _lib():
 
 def test_set2set_symbols_and_versions():
     from tf_geometric_amd import _lib as L
-    lib = L.load_library()
-    names = _declared_functions()
-    assert names == ["tfgx_lstm_sequence_backward_f32", "tfgx_lstm_sequence_f32", "tfgx_lstm_sequence_kernel_resident",
-                     "tfgx_lstm_sequence_saved_bytes", "tfgx_set2set_attend_backward_f32", "tfgx_set2set_attend_f32",
-                     "tfgx_set2set_attend_workspace_bytes", "tfgx_set2set_version"]
-    for name in names:
-        assert hasattr(lib, name), "libtfgx.so does not export {}".format(name)
-        assert getattr(lib, name).argtypes is not None, "{} is not bound".format(name)
-    assert set(names) == set(L.SET2SET_SIGNATURES), set(names) ^ set(L.SET2SET_SIGNATURES)
-    assert lib.tfgx_set2set_version() == L.SET2SET_ABI_VERSION == 1
-    src = open(HEADER).read()
-    assert re.search(r"#define\s+TFGX_SET2SET_ABI_VERSION\s+1\b", src)
-    assert re.search(r"#define\s+TFGX_SET2SET_CHUNK_ROWS\s+{}\b".format(L.SET2SET_CHUNK_ROWS), src)
-    assert re.search(r"#define\s+TFGX_SET2SET_MAX_FEATURES\s+{}\b".format(L.SET2SET_MAX_FEATURES), src)
-    assert lib.tfgx_lstm_version() == L.LSTM_ABI_VERSION == 1
-    assert re.search(r"#define\s+TFGX_LSTM_ABI_VERSION\s+1\b", open(os.path.join(ROOT, "include", "tfgx_lstm.h")).read())
-    assert lib.tfgx_version() == L.ABI_VERSION == 114
-    assert re.search(r"#define\s+TFGX_ABI_VERSION\s+114\b", open(os.path.join(ROOT, "include", "tfgx.h")).read())
+    assert sorted(declarations(HEADER)) == sorted(L.SET2SET_SIGNATURES) == [
+        "tfgx_lstm_sequence_backward_f32", "tfgx_lstm_sequence_f32", "tfgx_lstm_sequence_kernel_resident",
+        "tfgx_lstm_sequence_saved_bytes", "tfgx_set2set_attend_backward_f32", "tfgx_set2set_attend_f32",
+        "tfgx_set2set_attend_workspace_bytes", "tfgx_set2set_version"]
+    assert macro(HEADER, "TFGX_SET2SET_CHUNK_ROWS") == L.SET2SET_CHUNK_ROWS
+    assert macro(HEADER, "TFGX_SET2SET_MAX_FEATURES") == L.SET2SET_MAX_FEATURES
 
 
 def test_size_queries():
@@ -80,15 +61,6 @@ BIG_WS = 4 * (2 * 3 + 4 * (16 + 2))       # N = 4 * CHUNK, G = 3, F = 16
 
 def _call(fn, args):
     return fn(*args.values())
-
-
-def _refused(fn, ok, change, word):
-    """Every refusal happens on the host, before any device work (the pointers here are never dereferenced)."""
-    lib = _lib()
-    rc = _call(getattr(lib, fn), dict(ok, **change))
-    assert rc == 1, rc          # TFGX_ERR_INVALID_ARG
-    msg = lib.tfgx_last_error().decode()
-    assert word in msg and fn in msg, msg
 
 
 ATT_COMMON = [

@@ -4,6 +4,7 @@
 There is NO CPU fallback: if the library is missing, or there is no GPU, every operator raises.
 PyTorch is used only as plumbing: device memory (torch.Tensor), streams, torch.distributed.
 """
+import collections
 import ctypes
 import os
 
@@ -17,9 +18,6 @@ SUM, MEAN, MAX = 0, 1, 2
 ACT_NONE, ACT_RELU = 0, 1
 NORM_BOTH, NORM_LEFT, NORM_RIGHT = 0, 1, 2
 NORM_MODES = {"both": NORM_BOTH, "left": NORM_LEFT, "right": NORM_RIGHT}
-
-c_i32p = ctypes.c_void_p
-c_f32p = ctypes.c_void_p
 
 
 class TfgxError(RuntimeError):
@@ -141,7 +139,7 @@ class GatBackwardArgs(ctypes.Structure):
     ]
 
 
-# name -> (restype, argtypes); this table is checked against include/tfgx.h by tests/test_abi.py
+# name -> (restype, argtypes); every table is checked against its header, type by type, by tests/test_abi_registry.py
 _I64, _I32, _F32, _P, _SZ = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 SIGNATURES = {
     "tfgx_version": (ctypes.c_int, []),
@@ -243,8 +241,7 @@ SIGNATURES = {
     "tfgx_plan_source_blocks": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }
 
-# include/tfgx_h16.h (16-bit feature tables): its own header, its own version, its own table — checked against that header by
-# tests/test_h16_abi.py.  tfgx.h and SIGNATURES above do not know these names.
+# include/tfgx_h16.h (16-bit feature tables)
 H16_ABI_VERSION = 1
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 H16_DTYPES = {torch.bfloat16: DT_BF16, torch.float16: DT_F16}
@@ -257,8 +254,7 @@ H16_SIGNATURES = {
     "tfgx_h16_friendly_ld": (_I64, [_I64]),
 }
 
-# include/tfgx_fused_h16.h (the fused aggregate -> project launch over a 16-bit table): again its own header, version and table
-# — checked against that header by tests/test_fused_h16_abi.py.
+# include/tfgx_fused_h16.h (the fused aggregate -> project launch over a 16-bit table)
 FUSED_H16_ABI_VERSION = 1
 FUSED_H16_SIGNATURES = {
     "tfgx_fused_h16_version": (ctypes.c_int, []),
@@ -266,8 +262,7 @@ FUSED_H16_SIGNATURES = {
     "tfgx_aggregate_gemm_h16_describe": (ctypes.c_int, [ctypes.POINTER(ReduceArgs), _I32, _I64, ctypes.c_char_p, ctypes.c_size_t]),
 }
 
-# include/tfgx_gemm_h16.h (the dense GEMM and its weight gradient reading a 16-bit table): its own header, version and table —
-# checked against that header by tests/test_gemm_h16_abi.py.
+# include/tfgx_gemm_h16.h (the dense GEMM and its weight gradient reading a 16-bit table)
 GEMM_H16_ABI_VERSION = 1
 GEMM_H16_SIGNATURES = {
     "tfgx_gemm_h16_version": (ctypes.c_int, []),
@@ -286,8 +281,7 @@ class DropEdgePlan(ctypes.Structure):
                 ("out_row_ptr", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_perm", ctypes.c_void_p)]
 
 
-# include/tfgx_dropedge.h (DropEdge: edge dropout with sort-free plans): its own header, version and table — checked against
-# that header by tests/test_drop_edge_abi.py.
+# include/tfgx_dropedge.h (DropEdge: edge dropout with sort-free plans)
 DROPEDGE_ABI_VERSION = 1
 DROPEDGE_SIGNATURES = {
     "tfgx_dropedge_version": (ctypes.c_int, []),
@@ -298,8 +292,7 @@ DROPEDGE_SIGNATURES = {
                                            ctypes.POINTER(DropEdgePlan), ctypes.POINTER(DropEdgePlan), _P, _SZ, _P]),
 }
 
-# include/tfgx_linkpred.h (link prediction: the per-edge decoder and the negative samplers): its own header, version and
-# table — checked against that header by tests/test_linkpred_abi.py.
+# include/tfgx_linkpred.h (link prediction: the per-edge decoder and the negative samplers)
 LINKPRED_ABI_VERSION = 1
 NEGATIVE_BAD_START = -(1 << 31)     # TFGX_NEGATIVE_BAD_START as the int32 the device word is read as
 _U64, _U32 = ctypes.c_uint64, ctypes.c_uint32
@@ -311,8 +304,7 @@ LINKPRED_SIGNATURES = {
     "tfgx_negative_sample_from": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _U64, _U64, _I32, _P, _P, _P]),
 }
 
-# include/tfgx_lstm.h (the LSTM GraphSAGE aggregator: fused gather -> recurrence and its backward through time): its own
-# header, version and table — checked against that header by tests/test_lstm_abi.py.
+# include/tfgx_lstm.h (the LSTM GraphSAGE aggregator: fused gather -> recurrence and its backward through time)
 LSTM_ABI_VERSION = 1
 LSTM_MAX_UNITS = 256
 LSTM_SIGNATURES = {
@@ -324,8 +316,7 @@ LSTM_SIGNATURES = {
     "tfgx_lstm_aggregate_backward_f32": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _P, _P]),
 }
 
-# include/tfgx_set2set.h (Set2Set: the per-graph attention readout and the stateful sequence LSTM, each with its backward):
-# its own header, version and table — checked against that header by tests/test_set2set_abi.py.
+# include/tfgx_set2set.h (Set2Set: the per-graph attention readout and the stateful sequence LSTM, each with its backward)
 SET2SET_ABI_VERSION = 1
 SET2SET_CHUNK_ROWS = 512
 SET2SET_MAX_FEATURES = 1024
@@ -341,8 +332,7 @@ SET2SET_SIGNATURES = {
     "tfgx_lstm_sequence_backward_f32": (ctypes.c_int, [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P]),
 }
 
-# include/tfgx_asap.h (ASAP pooling: the fused 1-hop attention with its backward, and the sparse S^T A S of cluster_pool): its
-# own header, version and table — checked against that header by tests/test_asap_abi.py.
+# include/tfgx_asap.h (ASAP pooling: the fused 1-hop attention with its backward, and the sparse S^T A S of cluster_pool)
 ASAP_ABI_VERSION = 1
 ASAP_MAX_FEATURES = 256
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -358,8 +348,7 @@ ASAP_SIGNATURES = {
     "tfgx_spasp_reduce": (ctypes.c_int, [_I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
-# include/tfgx_seggram.h (the segmented transposed product S_g^T Y_g of DiffPool / MinCutPool and its backward): its own
-# header, version and table — checked against that header by tests/test_seggram_abi.py.
+# include/tfgx_seggram.h (the segmented transposed product S_g^T Y_g of DiffPool / MinCutPool and its backward)
 SEGGRAM_ABI_VERSION = 1
 SEGGRAM_MAX_K = 64
 SEGGRAM_BLOCK = 64
@@ -372,8 +361,7 @@ SEGGRAM_SIGNATURES = {
                                                       _I64, _P, _P]),
 }
 
-# include/tfgx_normgrad.h (the backward of the GCN normalisation: d/d raw edge weights): its own header, version and table —
-# checked against that header by tests/test_normgrad_abi.py.
+# include/tfgx_normgrad.h (the backward of the GCN normalisation: d/d raw edge weights)
 NORMGRAD_ABI_VERSION = 1
 NORMGRAD_ROW_PASS, NORMGRAD_COL_PASS, NORMGRAD_EDGE_PASS, NORMGRAD_ALL = 1, 2, 4, 7
 NORMGRAD_SIGNATURES = {
@@ -404,8 +392,7 @@ class CollateArgs(ctypes.Structure):
     ]
 
 
-# include/tfgx_collate.h (minibatch assembly out of a packed device dataset, with sort-free plans): its own header, version and
-# table — checked against that header by tests/test_collate_abi.py.
+# include/tfgx_collate.h (minibatch assembly out of a packed device dataset, with sort-free plans)
 COLLATE_ABI_VERSION = 1
 COLLATE_TILE = 1024          # TFGX_COLLATE_TILE: output elements per workgroup
 COLLATE_SIGNATURES = {
@@ -415,7 +402,7 @@ COLLATE_SIGNATURES = {
 }
 
 # include/tfgx_nbrblock.h (minibatch neighbour sampling: the row-list sampler and the order-stable relabel over a persistent
-# table): its own header, version and table — checked against that header by tests/test_nbrblock_abi.py.
+# table)
 NBRBLOCK_ABI_VERSION = 1
 NBRBLOCK_EMPTY = (1 << 31) - 1     # TFGX_NBRBLOCK_EMPTY: a table entry without a virtual id
 NBRBLOCK_BAD_RANGE, NBRBLOCK_BAD_REPEAT = 1, 2
@@ -428,11 +415,56 @@ NBRBLOCK_SIGNATURES = {
     "tfgx_nbrblock_reset": (ctypes.c_int, [_P, _I64, _P, _I64, _P]),
 }
 
+# One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
+# the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
+# registry; a new header is one more entry ("Adding a header").
+Abi = collections.namedtuple("Abi", "header version_fn version signatures constants")
+ABIS = (
+    Abi("tfgx.h", "tfgx_version", ABI_VERSION, SIGNATURES, ()),
+    Abi("tfgx_h16.h", "tfgx_h16_version", H16_ABI_VERSION, H16_SIGNATURES, ()),
+    Abi("tfgx_fused_h16.h", "tfgx_fused_h16_version", FUSED_H16_ABI_VERSION, FUSED_H16_SIGNATURES, ()),
+    Abi("tfgx_gemm_h16.h", "tfgx_gemm_h16_version", GEMM_H16_ABI_VERSION, GEMM_H16_SIGNATURES, ()),
+    Abi("tfgx_dropedge.h", "tfgx_dropedge_version", DROPEDGE_ABI_VERSION, DROPEDGE_SIGNATURES, ()),
+    Abi("tfgx_linkpred.h", "tfgx_linkpred_version", LINKPRED_ABI_VERSION, LINKPRED_SIGNATURES, ()),
+    Abi("tfgx_lstm.h", "tfgx_lstm_version", LSTM_ABI_VERSION, LSTM_SIGNATURES, ()),
+    Abi("tfgx_set2set.h", "tfgx_set2set_version", SET2SET_ABI_VERSION, SET2SET_SIGNATURES, ()),
+    Abi("tfgx_asap.h", "tfgx_asap_version", ASAP_ABI_VERSION, ASAP_SIGNATURES, ()),
+    Abi("tfgx_seggram.h", "tfgx_seggram_version", SEGGRAM_ABI_VERSION, SEGGRAM_SIGNATURES, (("tfgx_seggram_block", SEGGRAM_BLOCK),)),
+    Abi("tfgx_normgrad.h", "tfgx_normgrad_version", NORMGRAD_ABI_VERSION, NORMGRAD_SIGNATURES, ()),
+    Abi("tfgx_collate.h", "tfgx_collate_version", COLLATE_ABI_VERSION, COLLATE_SIGNATURES, (("tfgx_collate_tile", COLLATE_TILE),)),
+    Abi("tfgx_nbrblock.h", "tfgx_nbrblock_version", NBRBLOCK_ABI_VERSION, NBRBLOCK_SIGNATURES, ()),
+)
+
+# C struct name -> its ctypes mirror: every ctypes.Structure of this module
+STRUCTS = {
+    "tfgx_reduce_args": ReduceArgs, "tfgx_gat_args": GatArgs, "tfgx_hub_lists": HubLists,
+    "tfgx_gat_backward_args": GatBackwardArgs, "tfgx_drop_edge_plan": DropEdgePlan, "tfgx_collate_plan": CollatePlan,
+    "tfgx_collate_args": CollateArgs,
+}
+
+
+def bind(lib, abis=ABIS):
+    """Set restype / argtypes of every table of `abis` on `lib` (a ctypes.CDLL), then compare what the library was built with
+    against what this package binds: each header's version and each of its constants.  Returns lib."""
+    for abi in abis:
+        for name, (res, args) in abi.signatures.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
+    for abi in abis:
+        for name, bound in ((abi.version_fn, abi.version),) + tuple(abi.constants):
+            built = getattr(lib, name)()
+            if built != bound:
+                raise TfgxError("tf_geometric_amd: {} was built with {}() = {} but this package binds {} (include/{}): "
+                                "rebuild with __graft_entry__.build()".format(lib._name, name, built, bound, abi.header))
+    return lib
+
+
 _lib = None
 
 
 def load_library():
-    """Load libtfgx.so and bind every entry point of include/tfgx.h. Raises if it is not built."""
+    """Load libtfgx.so and bind() every header of ABIS. Raises if it is not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -446,111 +478,8 @@ def load_library():
         raise TfgxError(
             "tf_geometric_amd: HIP library {} is missing. Build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback.".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in H16_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in FUSED_H16_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in GEMM_H16_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in DROPEDGE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in LINKPRED_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in LSTM_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in SET2SET_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in ASAP_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in SEGGRAM_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in NORMGRAD_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in COLLATE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in NBRBLOCK_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.tfgx_nbrblock_version() != NBRBLOCK_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_nbrblock ABI {} but this package binds {} "
-                        "(include/tfgx_nbrblock.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_nbrblock_version(), NBRBLOCK_ABI_VERSION))
-    if lib.tfgx_collate_version() != COLLATE_ABI_VERSION or lib.tfgx_collate_tile() != COLLATE_TILE:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_collate ABI {} (tile {}) but this package binds {} (tile {}) "
-                        "(include/tfgx_collate.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_collate_version(), lib.tfgx_collate_tile(), COLLATE_ABI_VERSION, COLLATE_TILE))
-    if lib.tfgx_normgrad_version() != NORMGRAD_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_normgrad ABI {} but this package binds {} "
-                        "(include/tfgx_normgrad.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_normgrad_version(), NORMGRAD_ABI_VERSION))
-    if lib.tfgx_seggram_version() != SEGGRAM_ABI_VERSION or lib.tfgx_seggram_block() != SEGGRAM_BLOCK:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_seggram ABI {} (block {}) but this package binds {} (block {}) "
-                        "(include/tfgx_seggram.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_seggram_version(), lib.tfgx_seggram_block(), SEGGRAM_ABI_VERSION, SEGGRAM_BLOCK))
-    if lib.tfgx_asap_version() != ASAP_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_asap ABI {} but this package binds {} "
-                        "(include/tfgx_asap.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_asap_version(), ASAP_ABI_VERSION))
-    if lib.tfgx_set2set_version() != SET2SET_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_set2set ABI {} but this package binds {} "
-                        "(include/tfgx_set2set.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_set2set_version(), SET2SET_ABI_VERSION))
-    if lib.tfgx_lstm_version() != LSTM_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_lstm ABI {} but this package binds {} "
-                        "(include/tfgx_lstm.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_lstm_version(), LSTM_ABI_VERSION))
-    if lib.tfgx_linkpred_version() != LINKPRED_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_linkpred ABI {} but this package binds {} "
-                        "(include/tfgx_linkpred.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_linkpred_version(), LINKPRED_ABI_VERSION))
-    if lib.tfgx_dropedge_version() != DROPEDGE_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_dropedge ABI {} but this package binds {} "
-                        "(include/tfgx_dropedge.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_dropedge_version(), DROPEDGE_ABI_VERSION))
-    if lib.tfgx_gemm_h16_version() != GEMM_H16_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_gemm_h16 ABI {} but this package binds {} "
-                        "(include/tfgx_gemm_h16.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_gemm_h16_version(), GEMM_H16_ABI_VERSION))
-    if lib.tfgx_fused_h16_version() != FUSED_H16_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_fused_h16 ABI {} but this package binds {} "
-                        "(include/tfgx_fused_h16.h): rebuild with __graft_entry__.build()".format(
-                            LIB_PATH, lib.tfgx_fused_h16_version(), FUSED_H16_ABI_VERSION))
-    if lib.tfgx_h16_version() != H16_ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for tfgx_h16 ABI {} but this package binds {} (include/tfgx_h16.h): "
-                        "rebuild with __graft_entry__.build()".format(LIB_PATH, lib.tfgx_h16_version(), H16_ABI_VERSION))
-    if lib.tfgx_version() != ABI_VERSION:
-        raise TfgxError("tf_geometric_amd: {} was built for ABI {} but this package binds ABI {} (include/tfgx.h "
-                        "TFGX_ABI_VERSION): rebuild with __graft_entry__.build()".format(LIB_PATH, lib.tfgx_version(), ABI_VERSION))
-    _lib = lib
-    return lib
+    _lib = bind(ctypes.CDLL(LIB_PATH))
+    return _lib
 
 
 def check(rc, what=""):
