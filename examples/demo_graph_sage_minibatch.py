@@ -4,7 +4,10 @@ sampled 2-hop neighbourhood (fan-outs 25, 10 as num_sampled_neighbors_list of th
 each layer a small relabelled block with its CSR plan attached — the work of a step is proportional to the batch, not to the
 graph (include/tfgx_nbrblock.h).  The graph is a planted-partition graph (tf_geometric_amd.synthetic): node classification.
 
-    python examples/demo_graph_sage_minibatch.py [--epochs 5] [--batch 256]
+--fuse-input-hop leaves the outermost hop to the fused sample-and-reduce kernel (include/tfgx_samplereduce.h): it is drawn and
+reduced straight out of the feature table, and layer 0 finishes on the destination rows only (MeanGraphSage.combine).
+
+    python examples/demo_graph_sage_minibatch.py [--epochs 5] [--batch 256] [--fuse-input-hop]
 """
 import argparse
 import os
@@ -21,7 +24,7 @@ from tf_geometric_amd.utils import RandomNeighborSampler   # noqa: E402
 FANOUTS = [25, 10]               # fanouts[l] belongs to layer l, input side first
 
 
-def main(epochs=5, batch=256, num_nodes=20000, classes=6, quiet=False):
+def main(epochs=5, batch=256, num_nodes=20000, classes=6, quiet=False, fuse_input_hop=False):
     torch.manual_seed(0)
     x_np, ei_np, y_np = planted_partition_graph(num_nodes, classes=classes, degree=12, features=32, seed=0)
     # extra feature noise: a node's own row says little about its class, the mean over its (mostly same-class) neighbours does
@@ -34,7 +37,16 @@ def main(epochs=5, batch=256, num_nodes=20000, classes=6, quiet=False):
               tfg.layers.MeanGraphSage(units=64, activation=tfg.relu, concat=True).trainable(True)]
     fc = torch.nn.Linear(64, classes).cuda()
 
+    def forward_fused(seeds, training):
+        mb = sampler.sample_blocks(seeds, FANOUTS, fuse_input_hop=True)      # the hops but the outermost; one host read fewer
+        h = layers[0].combine([mb.gather(x), mb.input_aggregate(x, "mean")], training=training)
+        for layer, b in zip(layers[1:], mb.blocks):
+            h = layer([h[:b.num_src], b.edge_index, b.edge_weight], training=training)[:b.num_dst]
+        return fc(h)
+
     def forward(seeds, training):
+        if fuse_input_hop:
+            return forward_fused(seeds, training)
         mb = sampler.sample_blocks(seeds, FANOUTS)                  # a fresh sample per step (seed from torch's generator)
         h = mb.gather(x)
         for layer, b in zip(layers, mb.blocks):
@@ -67,5 +79,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--fuse-input-hop", action="store_true", help="draw and reduce the outermost hop in one launch")
     args = ap.parse_args()
-    main(epochs=args.epochs, batch=args.batch)
+    main(epochs=args.epochs, batch=args.batch, fuse_input_hop=args.fuse_input_hop)

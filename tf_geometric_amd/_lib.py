@@ -415,6 +415,17 @@ NBRBLOCK_SIGNATURES = {
     "tfgx_nbrblock_reset": (ctypes.c_int, [_P, _I64, _P, _I64, _P]),
 }
 
+# include/tfgx_samplereduce.h (the fused input hop of minibatch GraphSAGE: draw a listed node's neighbours and reduce their
+# feature rows in one launch)
+SAMPLEREDUCE_ABI_VERSION = 1
+SAMPLEREDUCE_MAX_DRAWS = 256       # TFGX_SAMPLEREDUCE_MAX_DRAWS: the largest k whose drawn list the kernel keeps in LDS
+SAMPLEREDUCE_BAD_RANGE = NBRBLOCK_BAD_RANGE
+SAMPLEREDUCE_SIGNATURES = {
+    "tfgx_samplereduce_version": (ctypes.c_int, []),
+    "tfgx_samplereduce_f32": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I32, _I32, _U64, _P, _I64, _I64, _I32, _P, _I64, _P, _P,
+                                             _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry ("Adding a header").
@@ -433,6 +444,7 @@ ABIS = (
     Abi("tfgx_normgrad.h", "tfgx_normgrad_version", NORMGRAD_ABI_VERSION, NORMGRAD_SIGNATURES, ()),
     Abi("tfgx_collate.h", "tfgx_collate_version", COLLATE_ABI_VERSION, COLLATE_SIGNATURES, (("tfgx_collate_tile", COLLATE_TILE),)),
     Abi("tfgx_nbrblock.h", "tfgx_nbrblock_version", NBRBLOCK_ABI_VERSION, NBRBLOCK_SIGNATURES, ()),
+    Abi("tfgx_samplereduce.h", "tfgx_samplereduce_version", SAMPLEREDUCE_ABI_VERSION, SAMPLEREDUCE_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module

@@ -3,7 +3,7 @@
 (reference: layers/conv/graph_sage.py; weight names kept for checkpoint compatibility)."""
 from ...activations import relu
 from ...nn.conv.graph_sage import (mean_graph_sage, sum_graph_sage, gcn_graph_sage, mean_pool_graph_sage,
-                                   max_pool_graph_sage, lstm_graph_sage)
+                                   max_pool_graph_sage, lstm_graph_sage, graph_sage_combine)
 from .._base import Layer
 from ..rnn import LSTM
 
@@ -47,6 +47,16 @@ class _SelfNeighborSage(Layer):
         x, edge_index, edge_weight = _unpack(inputs)
         return type(self)._fn(x, edge_index, edge_weight, self.self_kernel, self.neighbor_kernel, bias=self.bias,
                               activation=self.activation, concat=self.concat, normalize=self.normalize, cache=cache)
+
+    def combine(self, inputs, training=None):
+        """:param inputs: [x_dst, reduced] — the destination rows and their neighbour reduction (this layer's: the mean for
+        MeanGraphSage, the sum for SumGraphSage), e.g. [mb.gather(x), mb.input_aggregate(x, "mean")] of a minibatch sampled with
+        fuse_input_hop=True.  The layer's output for those rows, with the weights `call` uses (built here on first use)."""
+        x, reduced = inputs
+        self._maybe_build([x])
+        return graph_sage_combine(x, reduced, self.self_kernel, self.neighbor_kernel, bias=self.bias, activation=self.activation,
+                                  concat=self.concat, normalize=self.normalize)
+
 
 
 class MeanGraphSage(_SelfNeighborSage):

@@ -83,6 +83,19 @@ def _combine(from_x_kernel, x, from_neigh_kernel, reduced, bias, activation, con
     return _tail(h, post, normalize)
 
 
+def graph_sage_combine(x, reduced, self_kernel, neighbor_kernel, bias=None, activation=None, concat=True, normalize=False):
+    """The end of mean / sum GraphSAGE from (x_dst, aggregate): x @ self_kernel and reduced @ neighbor_kernel into the halves of
+    the output (or added), bias and activation in the GEMM epilogues, l2-normalise (reference :43-58).  x [n, F] are the
+    destination rows and reduced [n, F] their neighbour reduction, wherever it came from — a minibatch's fused input hop
+    (SampledMinibatch.input_aggregate) reduces straight from the global table, and the layer then runs on the destination
+    rows only.  With gradients the route is autograd.dual_linear / linear, as inside the layers."""
+    x, reduced = L.as_f32(x), L.as_f32(reduced)
+    if x.dim() != 2 or tuple(x.shape) != tuple(reduced.shape):
+        raise ValueError("graph_sage_combine: x and reduced must both be [n, F], got {} and {}".format(
+            tuple(x.shape), tuple(reduced.shape)))
+    return _combine(L.as_f32(self_kernel), x, L.as_f32(neighbor_kernel), reduced, bias, activation, concat, normalize)
+
+
 def _neighbor_reduce(x, edge_index, edge_weight, op, cache):
     x = L.as_f32(x)
     n = int(x.shape[0])

@@ -8,7 +8,7 @@ from .. import _lib as L
 from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
 from .link import (negative_sampling, negative_sampling_with_start_node, edge_train_test_split, extract_unique_edge,
                    convert_edge_index_to_edge_hash, convert_edge_hash_to_edge_index, sorted_adjacency)
-from .minibatch import SampledMinibatch, SampledBlock, hop_seed
+from .minibatch import SampledMinibatch, SampledBlock, hop_seed, sample_reduce_route
 
 
 def add_self_loop_edge(edge_index, num_nodes, edge_weight=None, fill_weight=1.0):
@@ -250,7 +250,21 @@ class RandomNeighborSampler(object):
         from .minibatch import sample_rows
         return sample_rows(self, rows, k=k, ratio=ratio, padding=padding, seed=seed)
 
-    def sample_blocks(self, seeds, fanouts, padding=False, seed=None):
+    def sample_reduce(self, rows, x, k=None, op="mean", padding=False, seed=None, ratio=None, out=None, return_count=False):
+        """The input hop of a minibatch in one launch (include/tfgx_samplereduce.h): float32 [len(rows), F] on the device, row i
+        the `op` ("mean" / "sum") of w_j * x[c_j] over the neighbours (c_j, w_j) that sample_rows(rows, k=k, padding=padding,
+        seed=seed) lists for node rows[i] — drawn and reduced on chip, no list, no gathered copy of x.  A row without
+        neighbours (or k = 0) is zeros.  x: a float32 table with a row for every node of the sampler's graph.
+        minibatch.sample_reduce_route(k, x) names the route: "fused" for 0 <= k <= _lib.SAMPLEREDUCE_MAX_DRAWS and an x that
+        does not require grad (one host read: the verdict on `rows`); otherwise "composed" — sample_rows with the same seed,
+        then the reduction over that list, which carries d/dx.  k=None and ratio= have no fused form: ValueError.  A HalfRows:
+        TypeError.  An id outside the graph, or an x with too few rows: ValueError.  Refused inside a hipGraph capture.
+        out=: a float32 [len(rows), F] tensor with dense rows (a column block of a wider buffer) to write into;
+        return_count=True returns (out, int32 [len(rows)] draws per row)."""
+        from .minibatch import sample_reduce
+        return sample_reduce(self, rows, x, k, op=op, padding=padding, seed=seed, ratio=ratio, out=out, return_count=return_count)
+
+    def sample_blocks(self, seeds, fanouts, padding=False, seed=None, fuse_input_hop=False):
         """A minibatch for len(fanouts) layers as a SampledMinibatch: fanouts[l] neighbours per node for layer l (input side
         first, as num_sampled_neighbors_list of the reference's demo), so sampling runs outward from the seeds with
         fanouts[-1] first.  Hop h samples the rows node_index[:n_{h-1}] with seed hop_seeds[h-1] (minibatch.hop_seed) and
@@ -258,9 +272,12 @@ class RandomNeighborSampler(object):
         CSR plan attached.  Duplicate or out-of-range seeds: ValueError.  Device tensors out, whatever the sampler was built
         from.  One host read per hop plus one for the seeds' verdict; refused inside a hipGraph capture.  The relabel table is
         emptied at the end of every call; a call that raised midway leaves it marked and the next call refills it.
-        One sampler serves one stream at a time."""
+        One sampler serves one stream at a time.
+        fuse_input_hop=True leaves the outermost hop (fanouts[0]) unsampled for sample_reduce: the result has the blocks of
+        layers 1 .. L-1, node_index holds the nodes known after the inner hops, mb.input_hop = (k, padding, seed) and one host
+        read fewer; layer 0 is layer.combine([mb.gather(x), mb.input_aggregate(x, op)])."""
         from .minibatch import sample_blocks
-        return sample_blocks(self, seeds, fanouts, padding=padding, seed=seed)
+        return sample_blocks(self, seeds, fanouts, padding=padding, seed=seed, fuse_input_hop=fuse_input_hop)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,10 @@ RandomNeighborSampler.sample_blocks, and what they return.
 The reference trains GraphSAGE on sampled neighbourhoods (demo/demo_graph_sage.py: num_sampled_neighbors_list = [25, 10]) with
 a Python loop over nodes; here every hop is a handful of launches whose size is the batch: counts from row_ptr[rows], the
 row-list sampler (bit for bit the rows of RandomNeighborSampler.sample), and an order-stable relabel over a table the sampler
-keeps.  Nothing per call is proportional to the graph's nodes or edges."""
+keeps.  Nothing per call is proportional to the graph's nodes or edges.
+
+The outermost hop's ids are consumed once, by layer 0's neighbour reduction: RandomNeighborSampler.sample_reduce
+(include/tfgx_samplereduce.h) draws and reduces in one launch, and sample_blocks(fuse_input_hop=True) leaves that hop to it."""
 import numpy as np
 import torch
 
@@ -49,12 +52,26 @@ class SampledMinibatch(object):
             h = layer([h[:b.num_src], b.edge_index, b.edge_weight], training=True)[:b.num_dst]
     """
 
-    def __init__(self, blocks, node_index, num_seeds, hop_seeds, num_host_syncs=0):
+    def __init__(self, blocks, node_index, num_seeds, hop_seeds, num_host_syncs=0, input_hop=None, sampler=None):
         self.blocks = blocks
         self.node_index = node_index
         self.num_seeds = int(num_seeds)
         self.hop_seeds = list(hop_seeds)
         self.num_host_syncs = int(num_host_syncs)
+        # sample_blocks(fuse_input_hop=True): (k, padding, seed) of the outermost hop, which was NOT sampled — blocks then belong
+        # to layers 1 .. L-1, node_index holds the nodes known after the inner hops, and layer 0 is
+        #     h = layers[0].combine([mb.gather(x), mb.input_aggregate(x, "mean")], training=True)
+        self.input_hop = input_hop
+        self._sampler = sampler
+
+    def input_aggregate(self, x, op="mean"):
+        """The outermost hop, drawn and reduced in one launch: float32 [len(node_index), F], row i the `op` ("mean" / "sum")
+        over the neighbours node node_index[i] draws with the recorded (k, padding, seed) — what the unfused call's blocks[0]
+        reduces from gather(x).  No host read: the ids are the sampler's own."""
+        if self.input_hop is None:
+            raise ValueError("input_aggregate needs a minibatch of sample_blocks(..., fuse_input_hop=True)")
+        k, padding, seed = self.input_hop
+        return sample_reduce(self._sampler, self.node_index, x, k, op=op, padding=padding, seed=seed, _own_ids=True)
 
     def gather(self, x):
         """x[node_index] for a float32 feature table [N, F] (tfgx_gather_rows_f32; a table that is being trained goes through
@@ -176,22 +193,15 @@ def _check_total(total):
         raise ValueError("the sample holds {} edges: more than int32 indexes".format(total))
 
 
-def sample_rows(sampler, rows, k=None, ratio=None, padding=False, seed=None):
-    if k is not None and ratio is not None:
-        raise Exception("k and ratio cannot be provided simultaneously")
-    _check_ids(rows, "rows")
-    L.require_gpu()
-    refuse_capture("RandomNeighborSampler.sample_rows")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+def _sample_rows_device(sampler, rows, k, ratio, padding, seed, who):
+    """sample_rows on the device: (edge_index [2, E], edge_weight [E], out_ptr [n_rows + 1])."""
     st = _state(sampler)
     dev = st.table.device
     rows_t, wide_bad = _ids_on_device(rows, st.n_nodes, dev)
     n_rows = int(rows_t.shape[0])
     if n_rows == 0:
-        ei = torch.zeros((2, 0), dtype=torch.int32, device=dev)
-        ew = torch.zeros(0, dtype=torch.float32, device=dev)
-        return (ei.cpu().numpy(), ew.cpu().numpy()) if sampler._numpy else (ei, ew)
+        return (torch.zeros((2, 0), dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                torch.zeros(1, dtype=torch.int32, device=dev))
     cnt = _counts(_degrees(st, rows_t), k, ratio, padding)
     out_ptr, total_dev = _out_ptr(cnt)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -201,22 +211,130 @@ def sample_rows(sampler, rows, k=None, ratio=None, padding=False, seed=None):
     _check_total(total)
     out_col, out_w = _launch_sample(sampler, st, rows_t, n_rows, out_ptr, total, padding, seed, flag)
     if int(flag.item()) != 0:
-        raise ValueError("sample_rows: a row id is outside [0, {})".format(st.n_nodes))
-    ei = torch.stack([_row_positions(cnt, n_rows, total), out_col])
-    if sampler._numpy:
-        return ei.cpu().numpy(), out_w.cpu().numpy()
-    return ei, out_w.contiguous()
+        raise ValueError("{}: a row id is outside [0, {})".format(who, st.n_nodes))
+    return torch.stack([_row_positions(cnt, n_rows, total), out_col]), out_w.contiguous(), out_ptr
 
 
-def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None):
+def sample_rows(sampler, rows, k=None, ratio=None, padding=False, seed=None):
+    if k is not None and ratio is not None:
+        raise Exception("k and ratio cannot be provided simultaneously")
+    _check_ids(rows, "rows")
+    L.require_gpu()
+    refuse_capture("RandomNeighborSampler.sample_rows")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    ei, ew, _ = _sample_rows_device(sampler, rows, k, ratio, padding, seed, "sample_rows")
+    return (ei.cpu().numpy(), ew.cpu().numpy()) if sampler._numpy else (ei, ew)
+
+
+# ---- the fused input hop (include/tfgx_samplereduce.h) ------------------------------------------------------------------
+_OPS = {"mean": L.MEAN, "sum": L.SUM}
+
+
+def check_sample_reduce_args(k, ratio=None):
+    """The refusals of sample_reduce that need no device."""
+    if ratio is not None:
+        raise ValueError("sample_reduce has no fused form for ratio= sampling (the kernel keeps at most {} draws per row on chip): "
+                         "pass k, or reduce the list of sample_rows(ratio=...)".format(L.SAMPLEREDUCE_MAX_DRAWS))
+    if k is None:
+        raise ValueError("sample_reduce has no fused form for k=None (every neighbour: a row may be as long as the graph): "
+                         "pass k, or reduce the whole graph with segment_reduce")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, got {!r}".format(k))
+    if k < 0:
+        raise ValueError("k must not be negative, got {}".format(k))
+
+
+def sample_reduce_route(k, x):
+    """"fused" (one launch of tfgx_samplereduce_f32) or "composed" (sample_rows, then the reduction over the list, which
+    carries d/dx): what sample_reduce itself dispatches on."""
+    check_sample_reduce_args(k)
+    trained = isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+    return "fused" if int(k) <= L.SAMPLEREDUCE_MAX_DRAWS and not trained else "composed"
+
+
+def _check_out(out, n_rows, F, dev):
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and out.dim() == 2
+            and tuple(out.shape) == (n_rows, F) and (n_rows == 0 or out.stride(1) == 1) and (n_rows <= 1 or out.stride(0) >= F)):
+        raise ValueError("sample_reduce: out must be a float32 [{}, {}] tensor on {} with dense rows".format(n_rows, F, dev))
+
+
+def sample_reduce(sampler, rows, x, k, op="mean", padding=False, seed=None, ratio=None, out=None, return_count=False,
+                  _own_ids=False):
+    from ..plan import CsrPlan, HalfRows, segment_reduce
+    check_sample_reduce_args(k, ratio)
+    if op not in _OPS:
+        raise ValueError("sample_reduce: op must be 'mean' or 'sum', got {!r}".format(op))
+    if isinstance(x, HalfRows):
+        raise TypeError("sample_reduce takes a float32 table, got a HalfRows (16-bit tables are out of scope here: pass x.float())")
+    if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
+        raise TypeError("sample_reduce takes a float32 table, got {}".format(x.dtype))
+    _check_ids(rows, "rows")
+    lib = L.require_gpu()
+    refuse_capture("RandomNeighborSampler.sample_reduce")
+    route = sample_reduce_route(k, x)
+    x = L.as_f32(x)
+    st = _state(sampler)
+    if x.dim() != 2 or int(x.shape[1]) < 1:
+        raise ValueError("sample_reduce: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
+    if int(x.shape[0]) < st.n_nodes:
+        raise ValueError("sample_reduce: x has {} rows but the sampler's graph has {} nodes".format(int(x.shape[0]), st.n_nodes))
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    dev, F = st.table.device, int(x.shape[1])
+    if route == "composed":
+        ei, ew, out_ptr = _sample_rows_device(sampler, rows, int(k), None, padding, seed, "sample_reduce")
+        n_rows = int(out_ptr.shape[0]) - 1
+        count = out_ptr[1:] - out_ptr[:-1]
+        if out is not None:
+            _check_out(out, n_rows, F, dev)
+        if n_rows == 0:
+            res = torch.empty((0, F), dtype=torch.float32, device=dev) if out is None else out
+        else:
+            plan = CsrPlan.from_sorted(out_ptr, ei[1], int(x.shape[0]), edge_index=ei)      # global column ids: x is the table
+            if x.requires_grad and torch.is_grad_enabled():
+                if out is not None:
+                    raise ValueError("sample_reduce: out= cannot be given for an x that requires grad")
+                from .. import autograd as AG
+                res = AG.aggregate(plan, x, _OPS[op], ew)
+            else:
+                res = segment_reduce(plan, x, _OPS[op], w_csr=ew, out=out)
+        return (res, count) if return_count else res
+    rows_t, wide_bad = _ids_on_device(rows, st.n_nodes, dev)
+    n_rows = int(rows_t.shape[0])
+    if out is None:
+        out = torch.empty((n_rows, F), dtype=torch.float32, device=dev)
+    else:
+        _check_out(out, n_rows, F, dev)
+    count = torch.zeros(n_rows, dtype=torch.int32, device=dev) if return_count else None
+    if n_rows == 0:
+        return (out, count) if return_count else out
+    x2, ldx = L.row_major_2d(x)
+    ldo = int(out.stride(0)) if n_rows > 1 else F
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if wide_bad is not None:
+        flag |= wide_bad
+    L.check(lib.tfgx_samplereduce_f32(
+        L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(rows_t), n_rows, int(k),
+        1 if padding else 0, int(seed), L.ptr(x2), ldx, F, _OPS[op], L.ptr(out), ldo, L.ptr(count), L.ptr(flag), L.stream_ptr()),
+        "tfgx_samplereduce_f32")
+    # the one host read: the verdict on `rows` (not taken for ids the sampler produced itself)
+    if not _own_ids and int(flag.item()) != 0:
+        raise ValueError("sample_reduce: a row id is outside [0, {})".format(st.n_nodes))
+    return (out, count) if return_count else out
+
+
+def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None, fuse_input_hop=False):
     from ..plan import CsrPlan, attach_plan
     check_sample_blocks_args(seeds, fanouts)
     lib = L.require_gpu()
     refuse_capture("RandomNeighborSampler.sample_blocks")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-    n_hops = len(fanouts)
-    hop_seeds = [hop_seed(seed, h) for h in range(n_hops)]
+    hop_seeds = [hop_seed(seed, h) for h in range(len(fanouts))]
+    # fuse_input_hop: the outermost hop (fanouts[0], the last seed) is left to sample_reduce; the hops before it run as ever
+    n_hops = len(fanouts) - (1 if fuse_input_hop else 0)
+    input_hop = (int(fanouts[0]), bool(padding), hop_seeds[-1]) if fuse_input_hop else None
     st = _state(sampler)
     dev = st.table.device
     if st.dirty:             # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
@@ -260,7 +378,7 @@ def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None):
             # brings both the new-node total and the next hop's edge total
             live = torch.arange(n_known + total, device=dev) < (n_known + n_new_dev[0])
             deg = torch.where(live, _degrees(st, grown), torch.zeros_like(grown))
-            next_cnt = _counts(deg, int(fanouts[n_hops - 2 - h]), None, padding)
+            next_cnt = _counts(deg, int(fanouts[len(fanouts) - 2 - h]), None, padding)
             next_ptr, next_total_dev = _out_ptr(next_cnt)
             n_new, next_total = torch.stack([n_new_dev[0].long(), next_total_dev]).tolist()
         else:
@@ -279,4 +397,4 @@ def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None):
 
     L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node_list), n_known, stream), "tfgx_nbrblock_reset")
     st.dirty = False
-    return SampledMinibatch(blocks[::-1], node_list[:n_known].contiguous(), num_seeds, hop_seeds, syncs)
+    return SampledMinibatch(blocks[::-1], node_list[:n_known].contiguous(), num_seeds, hop_seeds, syncs, input_hop, sampler)
