@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
-           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip"]
+           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -36,7 +36,10 @@ def build(force=False, verbose=True):
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
                 "tfgx_misc.hip": [sample_hdr],
                 "tfgx_nbrblock.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
-                "tfgx_samplereduce.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h")],
+                "tfgx_samplereduce.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
+                                          os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
+                "tfgx_nbrstatic.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h"),
+                                       os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
                 "tfgx_gemm.hip": gemm_hdrs,
                 "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
                 "tfgx_fused.hip": fused_hdrs,

@@ -426,6 +426,22 @@ SAMPLEREDUCE_SIGNATURES = {
                                              _P]),
 }
 
+# include/tfgx_nbrstatic.h (fixed-shape minibatch sampling: capacities the host knows, run-time sizes on the device, no reads)
+NBRSTATIC_ABI_VERSION = 1
+NBRSTATIC_DEAD = -1                # TFGX_NBRSTATIC_DEAD: a dead seed slot / virtual node
+NBRSTATIC_BAD_RANGE, NBRSTATIC_BAD_REPEAT = NBRBLOCK_BAD_RANGE, NBRBLOCK_BAD_REPEAT
+NBRSTATIC_SIGNATURES = {
+    "tfgx_nbrstatic_version": (ctypes.c_int, []),
+    "tfgx_nbrstatic_seeds": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "tfgx_nbrstatic_hop_workspace_bytes": (_SZ, [_I64, _I32]),
+    "tfgx_nbrstatic_hop": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "tfgx_nbrstatic_transpose_workspace_bytes": (_SZ, [_I64, _I64]),
+    "tfgx_nbrstatic_transpose": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "tfgx_nbrstatic_gather_rows_f32": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "tfgx_nbrstatic_input_hop_f32": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I64, _I32, _P, _I64,
+                                                    _P, _P, _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry ("Adding a header").
@@ -445,6 +461,7 @@ ABIS = (
     Abi("tfgx_collate.h", "tfgx_collate_version", COLLATE_ABI_VERSION, COLLATE_SIGNATURES, (("tfgx_collate_tile", COLLATE_TILE),)),
     Abi("tfgx_nbrblock.h", "tfgx_nbrblock_version", NBRBLOCK_ABI_VERSION, NBRBLOCK_SIGNATURES, ()),
     Abi("tfgx_samplereduce.h", "tfgx_samplereduce_version", SAMPLEREDUCE_ABI_VERSION, SAMPLEREDUCE_SIGNATURES, ()),
+    Abi("tfgx_nbrstatic.h", "tfgx_nbrstatic_version", NBRSTATIC_ABI_VERSION, NBRSTATIC_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module

@@ -20,7 +20,15 @@ __device__ __forceinline__ int draw_below(uint64_t seed, uint64_t row, uint32_t 
     return static_cast<int>((uint64_t(draw_u32(seed, row, i)) * uint64_t(n)) >> 32);
 }
 
-constexpr int kSampleLongRow = 64;       // rows with more neighbours / draws than this get a whole wave (coalesced walks)
+// the sampling seed of hop `hop` (0 = next to the seeds) from a seed kept in DEVICE memory: utils.hop_seed's mixing,
+// (seed + (hop + 1) * 0x9E3779B97F4A7C15) mod 2^63, done by the kernel that draws (a wave-uniform address: one scalar load) —
+// a hipGraph replay reads the value the captured sequence left there, never one frozen into the graph
+__device__ __forceinline__ uint64_t hop_seed_from(const uint64_t* __restrict__ seed_dev, int hop)
+{
+    return (*seed_dev + uint64_t(hop + 1) * 0x9E3779B97F4A7C15ull) & 0x7FFFFFFFFFFFFFFFull;
+}
+
+constexpr int kSampleLongRow = 64;      // rows with more neighbours / draws than this get a whole wave (coalesced walks)
 
 constexpr int kFloydMax = 32;            // Floyd's O(m^2) duplicate check only for few draws; otherwise one O(d) selection pass
 

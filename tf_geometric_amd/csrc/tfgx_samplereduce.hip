@@ -15,6 +15,7 @@
 #include "tfgx_common.h"
 #include "tfgx_sample_rows.h"
 #include "../../include/tfgx_samplereduce.h"
+#include "../../include/tfgx_nbrstatic.h"
 
 namespace tfgx {
 namespace {
@@ -111,12 +112,15 @@ __device__ __forceinline__ int lanes_for(int ncols)      // log2 of the smallest
     return lg;
 }
 
-// VEC = 4: x's rows start on 16 bytes and F >= 4 — float4 loads for the first F / 4 * 4 columns, scalar ones for the rest
+// VEC = 4: x's rows start on 16 bytes and F >= 4 — float4 loads for the first F / 4 * 4 columns, scalar ones for the rest.
+// seed_dev != NULL (tfgx_nbrstatic_input_hop_f32): the seed is hop `hop`'s mix of the DEVICE word, and a negative row id is a
+// dead slot — a row of zeros, count 0, no flag — not a refusal.
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void samplereduce_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                              const float* __restrict__ w, int32_t n_nodes,
                                                              const int32_t* __restrict__ rows, int64_t n_rows, int tile_rows,
                                                              int k, int replace_when_short, uint64_t seed,
+                                                             const uint64_t* __restrict__ seed_dev, int hop,
                                                              const float* __restrict__ x, int64_t ldx, int F, int op,
                                                              float* __restrict__ out, int64_t ldo, int out_vec,
                                                              int32_t* __restrict__ out_count, int32_t* __restrict__ bad_flag)
@@ -126,6 +130,7 @@ __global__ __launch_bounds__(kBlock) void samplereduce_kernel(const int32_t* __r
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     int32_t* s_col = s_col_all[wave];
     float* s_w = s_w_all[wave];
+    if (seed_dev != nullptr) seed = hop_seed_from(seed_dev, hop);
     const int64_t n_tiles = (n_rows + tile_rows - 1) / tile_rows;
     const int64_t n_waves = int64_t(gridDim.x) * kWaves;
     for (int64_t tile = int64_t(blockIdx.x) * kWaves + wave; tile < n_tiles; tile += n_waves) {
@@ -136,7 +141,10 @@ __global__ __launch_bounds__(kBlock) void samplereduce_kernel(const int32_t* __r
         int s = 0, d = 0, m = 0, ok = 0;
         if (lane < n_tile) {
             r = rows[base + lane];
-            if (r < 0 || r >= n_nodes) {
+            if (r < 0 && seed_dev != nullptr) {
+                ok = 1;                                                  // a dead slot: zeros (m stays 0)
+                if (out_count != nullptr) out_count[base + lane] = 0;
+            } else if (r < 0 || r >= n_nodes) {
                 atomicOr(bad_flag, TFGX_SAMPLEREDUCE_BAD_RANGE);
             } else {
                 ok = 1;
@@ -199,28 +207,28 @@ using namespace tfgx;
 
 extern "C" int tfgx_samplereduce_version(void) { return TFGX_SAMPLEREDUCE_ABI_VERSION; }
 
-extern "C" int tfgx_samplereduce_f32(const int32_t* row_ptr, const int32_t* col, const float* w, int64_t n_nodes,
-                                     const int32_t* rows, int64_t n_rows, int32_t k, int32_t replace_when_short, uint64_t seed,
-                                     const float* x, int64_t ldx, int64_t F, int32_t op, float* out, int64_t ldo,
-                                     int32_t* out_count, int32_t* bad_flag, tfgx_stream_t stream)
+// both entry points: `fn` names the caller in every refusal; seed_dev NULL = the by-value seed
+static int samplereduce_launch(const char* fn, const int32_t* row_ptr, const int32_t* col, const float* w, int64_t n_nodes,
+                               const int32_t* rows, int64_t n_rows, int32_t k, int32_t replace_when_short, uint64_t seed,
+                               const uint64_t* seed_dev, int32_t hop, const float* x, int64_t ldx, int64_t F, int32_t op,
+                               float* out, int64_t ldo, int32_t* out_count, int32_t* bad_flag, tfgx_stream_t stream)
 {
-    TFGX_RANGE();
-    if (int rc = check_size(__func__, "n_nodes", n_nodes)) return rc;
-    if (int rc = check_size(__func__, "n_rows", n_rows)) return rc;
-    if (k < 0) return bad_arg(__func__, "k must not be negative", k);
-    if (k > TFGX_SAMPLEREDUCE_MAX_DRAWS) return bad_arg(__func__, "k is above TFGX_SAMPLEREDUCE_MAX_DRAWS = " TFGX_STR(TFGX_SAMPLEREDUCE_MAX_DRAWS), k);
-    if (F < 1) return bad_arg(__func__, "F must be at least 1", (long long)F);
-    if (int rc = check_size(__func__, "F", F)) return rc;
-    if (ldx < F) return bad_arg(__func__, "ldx must be at least F", (long long)ldx);
-    if (ldo < F) return bad_arg(__func__, "ldo must be at least F", (long long)ldo);
-    if (op != TFGX_SUM && op != TFGX_MEAN) return bad_arg(__func__, "op must be TFGX_SUM or TFGX_MEAN", op);
+    if (int rc = check_size(fn, "n_nodes", n_nodes)) return rc;
+    if (int rc = check_size(fn, "n_rows", n_rows)) return rc;
+    if (k < 0) return bad_arg(fn, "k must not be negative", k);
+    if (k > TFGX_SAMPLEREDUCE_MAX_DRAWS) return bad_arg(fn, "k is above TFGX_SAMPLEREDUCE_MAX_DRAWS = " TFGX_STR(TFGX_SAMPLEREDUCE_MAX_DRAWS), k);
+    if (F < 1) return bad_arg(fn, "F must be at least 1", (long long)F);
+    if (int rc = check_size(fn, "F", F)) return rc;
+    if (ldx < F) return bad_arg(fn, "ldx must be at least F", (long long)ldx);
+    if (ldo < F) return bad_arg(fn, "ldo must be at least F", (long long)ldo);
+    if (op != TFGX_SUM && op != TFGX_MEAN) return bad_arg(fn, "op must be TFGX_SUM or TFGX_MEAN", op);
     if (n_rows == 0) return TFGX_OK;
-    if (rows == nullptr) return null_arg(__func__, "rows");
-    if (out == nullptr) return null_arg(__func__, "out");
-    if (bad_flag == nullptr) return null_arg(__func__, "bad_flag");
-    if (n_nodes > 0 && row_ptr == nullptr) return null_arg(__func__, "row_ptr");
-    if (n_nodes > 0 && col == nullptr) return null_arg(__func__, "col");
-    if (n_nodes > 0 && x == nullptr) return null_arg(__func__, "x");
+    if (rows == nullptr) return null_arg(fn, "rows");
+    if (out == nullptr) return null_arg(fn, "out");
+    if (bad_flag == nullptr) return null_arg(fn, "bad_flag");
+    if (n_nodes > 0 && row_ptr == nullptr) return null_arg(fn, "row_ptr");
+    if (n_nodes > 0 && col == nullptr) return null_arg(fn, "col");
+    if (n_nodes > 0 && x == nullptr) return null_arg(fn, "x");
 
     const bool x_vec = F >= 4 && ldx % 4 == 0 && aligned_to(x, 16);
     const bool out_vec = ldo % 4 == 0 && aligned_to(out, 16);
@@ -238,13 +246,37 @@ extern "C" int tfgx_samplereduce_f32(const int32_t* row_ptr, const int32_t* col,
     const int grid = grid_for(n_tiles, kWaves);
     if (x_vec) {
         samplereduce_kernel<4><<<grid, kBlock, 0, as_stream(stream)>>>(
-            row_ptr, col, w, int32_t(n_nodes), rows, n_rows, int(tile_rows), k, replace_when_short, seed, x, ldx, int(F), op,
-            out, ldo, out_vec ? 1 : 0, out_count, bad_flag);
+            row_ptr, col, w, int32_t(n_nodes), rows, n_rows, int(tile_rows), k, replace_when_short, seed, seed_dev, hop, x, ldx,
+            int(F), op, out, ldo, out_vec ? 1 : 0, out_count, bad_flag);
     } else {
         samplereduce_kernel<1><<<grid, kBlock, 0, as_stream(stream)>>>(
-            row_ptr, col, w, int32_t(n_nodes), rows, n_rows, int(tile_rows), k, replace_when_short, seed, x, ldx, int(F), op,
-            out, ldo, 0, out_count, bad_flag);
+            row_ptr, col, w, int32_t(n_nodes), rows, n_rows, int(tile_rows), k, replace_when_short, seed, seed_dev, hop, x, ldx,
+            int(F), op, out, ldo, 0, out_count, bad_flag);
     }
     TFGX_LAUNCH_CHECK("samplereduce_kernel");
     return TFGX_OK;
+}
+
+extern "C" int tfgx_samplereduce_f32(const int32_t* row_ptr, const int32_t* col, const float* w, int64_t n_nodes,
+                                     const int32_t* rows, int64_t n_rows, int32_t k, int32_t replace_when_short, uint64_t seed,
+                                     const float* x, int64_t ldx, int64_t F, int32_t op, float* out, int64_t ldo,
+                                     int32_t* out_count, int32_t* bad_flag, tfgx_stream_t stream)
+{
+    TFGX_RANGE();
+    return samplereduce_launch(__func__, row_ptr, col, w, n_nodes, rows, n_rows, k, replace_when_short, seed, nullptr, 0, x, ldx,
+                               F, op, out, ldo, out_count, bad_flag, stream);
+}
+
+// include/tfgx_nbrstatic.h: the same launch with the seed read from the device and dead slots as rows of zeros
+extern "C" int tfgx_nbrstatic_input_hop_f32(const int32_t* row_ptr, const int32_t* col, const float* w, int64_t n_nodes,
+                                            const int32_t* node, int64_t n_rows, int32_t k, int32_t replace_when_short,
+                                            const uint64_t* seed, int32_t hop, const float* x, int64_t ldx, int64_t F, int32_t op,
+                                            float* out, int64_t ldo, int32_t* out_count, int32_t* bad_flag, tfgx_stream_t stream)
+{
+    TFGX_RANGE();
+    if (hop < 0) return bad_arg(__func__, "hop must not be negative", hop);
+    if (n_rows > 0 && node == nullptr) return null_arg(__func__, "node");
+    if (n_rows > 0 && seed == nullptr) return null_arg(__func__, "seed");
+    return samplereduce_launch(__func__, row_ptr, col, w, n_nodes, node, n_rows, k, replace_when_short, 0, seed, hop, x, ldx, F,
+                               op, out, ldo, out_count, bad_flag, stream);
 }

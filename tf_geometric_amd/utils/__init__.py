@@ -8,7 +8,8 @@ from .. import _lib as L
 from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
 from .link import (negative_sampling, negative_sampling_with_start_node, edge_train_test_split, extract_unique_edge,
                    convert_edge_index_to_edge_hash, convert_edge_hash_to_edge_index, sorted_adjacency)
-from .minibatch import SampledMinibatch, SampledBlock, hop_seed, sample_reduce_route
+from .minibatch import (SampledMinibatch, SampledBlock, hop_seed, sample_reduce_route, StaticMinibatch, StaticCapacities,
+                        static_capacities)
 
 
 def add_self_loop_edge(edge_index, num_nodes, edge_weight=None, fill_weight=1.0):
@@ -278,6 +279,21 @@ class RandomNeighborSampler(object):
         read fewer; layer 0 is layer.combine([mb.gather(x), mb.input_aggregate(x, op)])."""
         from .minibatch import sample_blocks
         return sample_blocks(self, seeds, fanouts, padding=padding, seed=seed, fuse_input_hop=fuse_input_hop)
+
+    def sample_blocks_static(self, seeds, fanouts, padding=False, seed=None, fuse_input_hop=False, ratio=None):
+        """sample_blocks with FIXED shapes (include/tfgx_nbrstatic.h): a StaticMinibatch whose every tensor has the size
+        static_capacities(len(seeds), fanouts) gives, whatever was drawn — no host read, so a step that samples can be
+        captured into a hipGraph (CapturedTrainStep).  seeds: a fixed-length int list; -1 is a dead slot (the short last batch).
+        Hop h over R rows at fan-out k has R * k edge slots, R * k new-node slots and R sink rows; a live row draws what
+        sample_rows gives that node with hop_seed(seed, h - 1), bit for bit; the unused edge slots are unit self-loops on the
+        dead sink rows, so every block is an ordinary square graph of exactly R * k edges whose both plans are attached.
+        node_index holds -1 for a dead virtual node, gather(x) a row of zeros; mask the loss with mb.seed_mask.
+        seed: an int, or an int64 one-element DEVICE tensor the kernels read when they run (advance it inside a captured
+        function: state.add_(1)); None draws one from torch's generator and is refused inside a capture.  A seed out of range
+        or repeated becomes a dead slot and is reported by mb.check() (the one host read, the caller's choice).  ratio= and a
+        fan-out of None have no capacity bound: ValueError.  One sampler serves one stream at a time."""
+        from .minibatch import sample_blocks_static
+        return sample_blocks_static(self, seeds, fanouts, padding=padding, seed=seed, fuse_input_hop=fuse_input_hop, ratio=ratio)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,13 @@ row-list sampler (bit for bit the rows of RandomNeighborSampler.sample), and an 
 keeps.  Nothing per call is proportional to the graph's nodes or edges.
 
 The outermost hop's ids are consumed once, by layer 0's neighbour reduction: RandomNeighborSampler.sample_reduce
-(include/tfgx_samplereduce.h) draws and reduces in one launch, and sample_blocks(fuse_input_hop=True) leaves that hop to it."""
+(include/tfgx_samplereduce.h) draws and reduces in one launch, and sample_blocks(fuse_input_hop=True) leaves that hop to it.
+
+sample_blocks reads its sizes back (L + 1 host reads) and cannot be captured.  RandomNeighborSampler.sample_blocks_static
+(include/tfgx_nbrstatic.h) is the same sample padded to capacities the host knows from (len(seeds), fanouts): no read, a fixed
+launch sequence, replayable from a hipGraph."""
+import collections
+
 import numpy as np
 import torch
 
@@ -398,3 +404,255 @@ def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None, fuse_input_
     L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node_list), n_known, stream), "tfgx_nbrblock_reset")
     st.dirty = False
     return SampledMinibatch(blocks[::-1], node_list[:n_known].contiguous(), num_seeds, hop_seeds, syncs, input_hop, sampler)
+
+
+# ---- fixed-shape sampling (include/tfgx_nbrstatic.h): no host read, hipGraph-capturable ---------------------------------
+StaticCapacities = collections.namedtuple("StaticCapacities", "rows edges sinks fanouts")
+StaticCapacities.__doc__ = """The sizes of sample_blocks_static, hop by hop outward from the seeds (hop h = 1 .. L uses
+fanouts[L - h]): rows[0] = B and rows[h] = R_h virtual nodes after hop h; edges[h - 1] = E_h = R_{h-1} * k_h, also the number
+of new-node slots; sinks[h - 1] = S_h = R_{h-1} (0 when k_h == 0); fanouts[h - 1] = k_h.  R_h = R_{h-1} + E_h + S_h."""
+
+
+def _capacities(B, ks):
+    """StaticCapacities for the hop-ordered fan-outs `ks`; refuses a total that int32 does not index."""
+    rows, edges, sinks = [int(B)], [], []
+    for k in ks:
+        R = rows[-1]
+        E, S = R * int(k), (R if int(k) > 0 else 0)
+        if R + E + S >= (1 << 31) - 1:
+            raise ValueError("static_capacities: {} seeds with fan-outs {} need {} virtual nodes after hop {}: more than int32 "
+                             "indexes".format(B, [int(v) for v in ks][::-1], R + E + S, len(edges) + 1))
+        rows.append(R + E + S)
+        edges.append(E)
+        sinks.append(S)
+    return StaticCapacities(rows, edges, sinks, [int(k) for k in ks])
+
+
+def check_static_args(fanouts, ratio=None):
+    """The refusals of sample_blocks_static that need neither the seeds nor a device."""
+    if ratio is not None:
+        raise ValueError("sample_blocks_static has no form for ratio= sampling (a row's list has no bound the host knows): pass "
+                         "fan-outs, or use sample_rows(ratio=...)")
+    if isinstance(fanouts, (list, tuple)) and any(f is None for f in fanouts):
+        raise ValueError("sample_blocks_static has no form for a fan-out of None (k=None keeps every neighbour: a row may be as "
+                         "long as the graph, so there is no capacity): pass integer fan-outs, or use sample_blocks")
+    if not isinstance(fanouts, (list, tuple)) or len(fanouts) == 0:
+        raise ValueError("fanouts must be a non-empty list of neighbour counts, one per layer (input side first)")
+    for f in fanouts:
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
+            raise ValueError("fanouts must be integers, got {!r}".format(f))
+        if f < 0:
+            raise ValueError("fanouts must not be negative, got {}".format(f))
+
+
+def static_capacities(B, fanouts):
+    """The shapes of sample_blocks_static(seeds of length B, fanouts), from the two arguments alone (StaticCapacities).
+    static_capacities(1024, [25, 10]).rows == [1024, 12288, 331776].  ValueError beyond int32."""
+    check_static_args(fanouts)
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or B < 0:
+        raise ValueError("static_capacities: B must be a non-negative integer, got {!r}".format(B))
+    return _capacities(int(B), [int(k) for k in fanouts][::-1])
+
+
+def _device_seed(seed, dev, who):
+    """The seed as one int64 on the device.  A tensor is used where it is (the kernels read it when they run); an int is
+    placed with a fill; None draws from torch's host generator, which a capture would freeze into the graph."""
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != dev:
+            raise ValueError("{}: a tensor seed must be one int64 on {}, got {} {} on {}".format(
+                who, dev, tuple(seed.shape), seed.dtype, seed.device))
+        return seed.detach().reshape(1)
+    if seed is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("{}: seed=None inside a hipGraph capture would freeze one by-value seed into the graph and every "
+                               "replay would draw the same sample: pass an int64 one-element device tensor and advance it inside "
+                               "the captured function (state.add_(1))".format(who))
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("{}: seed must be an int, an int64 one-element device tensor or None, got {!r}".format(who, seed))
+    s = int(seed) & ((1 << 64) - 1)
+    return torch.full((1,), s - (1 << 64) if s >= (1 << 63) else s, dtype=torch.int64, device=dev)
+
+
+def _no_fused_static(why):
+    return ValueError("sample_blocks_static: the fused input hop {}; use the composed dynamic route, sample_blocks(..., "
+                      "fuse_input_hop=True), whose input_aggregate falls back to sample_rows and a differentiable "
+                      "reduction".format(why))
+
+
+class StaticMinibatch(object):
+    """What sample_blocks_static returns.  blocks[l] belongs to layer l (input side first), each a square graph on its
+    num_src nodes with both CSR plans attached; node_index int32 [R_L] = the global id of a live virtual node, -1 for a dead
+    one (a dead seed slot, an unused new-node slot, a sink row); live = node_index >= 0; seed_mask = live[:num_seeds];
+    counts int32 [hops, 2] on the device = (sampled edges, new nodes) per hop outward; flag: the device word check() reads;
+    seed: the device seed the kernels read.  num_host_syncs == 0: nothing was read back.
+
+        h = mb.gather(x)                                   # zeros for dead rows
+        for layer, b in zip(layers, mb.blocks):
+            h = layer([h[:b.num_src], b.edge_index, b.edge_weight], training=True)[:b.num_dst]
+        loss = (per_seed_loss(h) * mb.seed_mask).sum() / mb.seed_mask.sum().clamp(min=1)
+    """
+
+    num_host_syncs = 0
+
+    def __init__(self, blocks, node_index, num_seeds, counts, flag, seed, capacities, n_nodes, input_hop=None, sampler=None):
+        self.blocks = blocks
+        self.node_index = node_index
+        self.num_seeds = int(num_seeds)
+        self.live = node_index >= 0
+        self.seed_mask = self.live[:self.num_seeds]
+        self.counts = counts
+        self.flag = flag
+        self.seed = seed
+        self.capacities = capacities
+        # fuse_input_hop=True: (k, padding, hop index) of the outermost hop, which was NOT sampled (blocks belong to layers 1 .. L-1)
+        self.input_hop = input_hop
+        self._n_nodes = int(n_nodes)
+        self._sampler = sampler
+
+    def check(self):
+        """The ONE host read of a static minibatch, when the caller wants it: the ValueErrors of sample_blocks — a seed outside
+        the graph (other than -1), seeds that repeat.  The offending slots are dead in this minibatch either way."""
+        bad = int(self.flag.item())
+        if bad & L.NBRSTATIC_BAD_RANGE:
+            raise ValueError("sample_blocks_static: a seed is outside [0, {})".format(self._n_nodes))
+        if bad & L.NBRSTATIC_BAD_REPEAT:
+            raise ValueError("sample_blocks_static: seeds must not repeat")
+        return self
+
+    def gather(self, x):
+        """float32 [R_L, F]: x[node_index] for the live rows, zeros for the dead ones (tfgx_nbrstatic_gather_rows_f32; a table
+        that is being trained goes through torch's indexing with a clamp and a mask, which carries the gradient)."""
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.float32:
+                raise TypeError("StaticMinibatch.gather takes a float32 table, got {}".format(x.dtype))
+            if x.requires_grad and torch.is_grad_enabled():
+                rows = x[self.node_index.clamp(min=0).long()]
+                return torch.where(self.live[:, None], rows, torch.zeros((), dtype=x.dtype, device=x.device))
+        lib = L.require_gpu()
+        x = L.as_f32(x)
+        if x.dim() != 2 or int(x.shape[1]) < 1:
+            raise ValueError("StaticMinibatch.gather: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
+        if int(x.shape[0]) < max(self._n_nodes, 1):
+            raise ValueError("StaticMinibatch.gather: x has {} rows but the sampler's graph has {} nodes".format(
+                int(x.shape[0]), self._n_nodes))
+        x2, ldx = L.row_major_2d(x)
+        M, F = int(self.node_index.shape[0]), int(x2.shape[1])
+        out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
+        L.check(lib.tfgx_nbrstatic_gather_rows_f32(L.ptr(x2), ldx, L.ptr(self.node_index), M, F, L.ptr(out), F, L.stream_ptr()),
+                "tfgx_nbrstatic_gather_rows_f32")
+        return out
+
+    def input_aggregate(self, x, op="mean"):
+        """The outermost hop, drawn and reduced in one launch with the seed read from the device: float32 [len(node_index), F],
+        row i the `op` ("mean" / "sum") over the neighbours node_index[i] draws — bit for bit what the dynamic minibatch's
+        input_aggregate gives that node — and zeros for a dead row.  No host read."""
+        if self.input_hop is None:
+            raise ValueError("input_aggregate needs a minibatch of sample_blocks_static(..., fuse_input_hop=True)")
+        if op not in _OPS:
+            raise ValueError("input_aggregate: op must be 'mean' or 'sum', got {!r}".format(op))
+        if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
+            raise _no_fused_static("takes a float32 table, got {}".format(x.dtype))
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise _no_fused_static("carries no gradient to a table that requires grad")
+        lib = L.require_gpu()
+        k, padding, hop = self.input_hop
+        st = _state(self._sampler)
+        x = L.as_f32(x)
+        if x.dim() != 2 or int(x.shape[1]) < 1:
+            raise ValueError("input_aggregate: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
+        if int(x.shape[0]) < st.n_nodes:
+            raise ValueError("input_aggregate: x has {} rows but the sampler's graph has {} nodes".format(int(x.shape[0]), st.n_nodes))
+        x2, ldx = L.row_major_2d(x)
+        M, F = int(self.node_index.shape[0]), int(x2.shape[1])
+        out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
+        L.check(lib.tfgx_nbrstatic_input_hop_f32(
+            L.ptr(st.row_ptr), L.ptr(self._sampler.plan.col), L.ptr(self._sampler.w_csr), st.n_nodes, L.ptr(self.node_index), M,
+            int(k), 1 if padding else 0, L.ptr(self.seed), int(hop), L.ptr(x2), ldx, F, _OPS[op], L.ptr(out), F, None,
+            L.ptr(self.flag), L.stream_ptr()), "tfgx_nbrstatic_input_hop_f32")
+        return out
+
+
+def _static_seeds_on_device(seeds, n_nodes, dev):
+    """int32 seeds on the device without a read: an id wider than int32 is clamped to an out-of-range int32 first (the kernel
+    then flags it as it flags any other)."""
+    t = seeds if isinstance(seeds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds)))
+    t = t.detach().to(dev).reshape(-1)
+    if t.dtype != torch.int32:
+        t = t.long().clamp(min=-2, max=n_nodes).to(torch.int32)
+    return t.contiguous()
+
+
+def sample_blocks_static(sampler, seeds, fanouts, padding=False, seed=None, fuse_input_hop=False, ratio=None):
+    from ..plan import CsrPlan, attach_plan, hub_policy
+    check_static_args(fanouts, ratio)
+    _check_ids(seeds, "seeds")
+    who = "RandomNeighborSampler.sample_blocks_static"
+    n_layers = len(fanouts)
+    k_input = int(fanouts[0])
+    if fuse_input_hop and k_input > L.SAMPLEREDUCE_MAX_DRAWS:
+        raise _no_fused_static("keeps at most {} draws per row on chip, got fanouts[0] = {}".format(L.SAMPLEREDUCE_MAX_DRAWS, k_input))
+    lib = L.require_gpu()
+    st = getattr(sampler, "_nbrblock", None)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("{}: the sampler's row_ptr and relabel table are made on its first call, which cannot be a captured "
+                               "one: call it once eagerly before the capture (the warm-up of CapturedTrainStep does)".format(who))
+        st = _state(sampler)
+    dev = st.table.device
+    seed_t = _device_seed(seed, dev, who)
+    seeds_t = _static_seeds_on_device(seeds, st.n_nodes, dev)
+    B = int(seeds_t.shape[0])
+    # fuse_input_hop: the outermost hop (fanouts[0], hop index L - 1) is left to input_aggregate
+    ks = [int(k) for k in (fanouts[1:] if fuse_input_hop else fanouts)][::-1]
+    cap = _capacities(B, ks)
+    input_hop = (k_input, bool(padding), n_layers - 1) if fuse_input_hop else None
+    if st.dirty:             # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
+        st.table.fill_(L.NBRBLOCK_EMPTY)
+    st.dirty = True
+    stream = L.stream_ptr()
+    n_total = cap.rows[-1]
+    node = torch.empty(n_total, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = torch.zeros((len(ks), 2), dtype=torch.int32, device=dev)
+    L.check(lib.tfgx_nbrstatic_seeds(L.ptr(st.table), st.n_nodes, L.ptr(seeds_t), B, L.ptr(node), L.ptr(flag), stream),
+            "tfgx_nbrstatic_seeds")
+    blocks = []
+    for h, k in enumerate(ks):
+        R, E, Rn = cap.rows[h], cap.edges[h], cap.rows[h + 1]
+        if R == 0:
+            brp = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            brp = torch.empty(Rn + 1, dtype=torch.int32, device=dev)
+        ei = torch.empty((2, E), dtype=torch.int32, device=dev)
+        ew = torch.empty(E, dtype=torch.float32, device=dev)
+        ws_bytes = lib.tfgx_nbrstatic_hop_workspace_bytes(R, k)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        L.check(lib.tfgx_nbrstatic_hop(
+            L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(st.table), L.ptr(node), R, k,
+            1 if padding else 0, L.ptr(seed_t), h, L.ptr(brp), L.ptr(ei[0]), L.ptr(ei[1]), L.ptr(ew), L.ptr(counts[h]), L.ptr(ws),
+            ws_bytes, stream), "tfgx_nbrstatic_hop")
+        # both plans, no sort of the list by destination (brp IS the row_ptr, sink and empty rows included) and no host read
+        plan = CsrPlan.from_sorted(brp, ei[1], Rn, edge_index=ei)
+        t_row_ptr = torch.empty(Rn + 1, dtype=torch.int32, device=dev)
+        t_col = torch.empty(E, dtype=torch.int32, device=dev)
+        t_perm = torch.empty(E, dtype=torch.int32, device=dev)
+        tws_bytes = lib.tfgx_nbrstatic_transpose_workspace_bytes(E, Rn)
+        tws = torch.empty(max(tws_bytes, 1), dtype=torch.uint8, device=dev)
+        L.check(lib.tfgx_nbrstatic_transpose(L.ptr(ei[0]), L.ptr(ei[1]), E, Rn, L.ptr(t_row_ptr), L.ptr(t_col), L.ptr(t_perm),
+                                             L.ptr(tws), tws_bytes, stream), "tfgx_nbrstatic_transpose")
+        if Rn == 0:
+            t_row_ptr.zero_()
+        pt = CsrPlan(t_row_ptr, t_col, t_perm, Rn, Rn, E)
+        plan._transposed, pt._transposed = pt, plan
+        # no destination row is longer than k: where that is within the hub threshold the plan has no hub rows, and the walk
+        # order (a speed-up of skewed plans; results do not depend on it) is left out — neither is computed, neither reads back.
+        # The transposed plan (a popular source may be long) keeps its lazy metadata.
+        thr, _ = hub_policy(E, Rn)
+        if k <= thr:
+            plan.hub_threshold, plan._hub, plan._row_order = thr, False, False
+        attach_plan(ei, plan)
+        blocks.append(SampledBlock(ei, ew, R, Rn))
+    L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node), n_total, stream), "tfgx_nbrblock_reset")
+    st.dirty = False
+    return StaticMinibatch(blocks[::-1], node, B, counts, flag, seed_t, cap, st.n_nodes, input_hop, sampler)
