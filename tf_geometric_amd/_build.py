@@ -32,24 +32,27 @@ def build(force=False, verbose=True):
     # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
     fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
     gemm_hdrs = [os.path.join(CSRC, "tfgx_gemm_kernels.h"), os.path.join(CSRC, "tfgx_mfma.h")]      # the GEMM templates both GEMM sources instantiate
-    sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's per-row bodies: both samplers are compiled from it
+    sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's bodies and kernel pair: every sampler is compiled from it
+    host_hdr = os.path.join(CSRC, "tfgx_host.h")               # the refusals and workspace layouts of the entry points
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
                 "tfgx_misc.hip": [sample_hdr],
-                "tfgx_nbrblock.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
-                "tfgx_samplereduce.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
+                "tfgx_plan.hip": [host_hdr], "tfgx_plan_ext.hip": [host_hdr], "tfgx_subgraph.hip": [host_hdr],
+                "tfgx_topk.hip": [host_hdr], "tfgx_poolgrad.hip": [host_hdr],
+                "tfgx_nbrblock.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
+                "tfgx_samplereduce.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
                                           os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
-                "tfgx_nbrstatic.hip": [sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h"),
+                "tfgx_nbrstatic.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h"),
                                        os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
                 "tfgx_gemm.hip": gemm_hdrs,
                 "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
                 "tfgx_fused.hip": fused_hdrs,
                 "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr] + fused_hdrs,
-                "tfgx_dropedge.hip": [os.path.join(_HERE, "..", "include", "tfgx_dropedge.h")],
+                "tfgx_dropedge.hip": [host_hdr, os.path.join(_HERE, "..", "include", "tfgx_dropedge.h")],
                 "tfgx_linkpred.hip": [os.path.join(_HERE, "..", "include", "tfgx_linkpred.h")],
                 "tfgx_lstm.hip": [os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],
                 "tfgx_set2set.hip": [os.path.join(_HERE, "..", "include", "tfgx_set2set.h"),
                                      os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],
-                "tfgx_asap.hip": [os.path.join(_HERE, "..", "include", "tfgx_asap.h")],
+                "tfgx_asap.hip": [host_hdr, os.path.join(_HERE, "..", "include", "tfgx_asap.h")],
                 "tfgx_seggram.hip": [os.path.join(_HERE, "..", "include", "tfgx_seggram.h")],
                 "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")],
                 "tfgx_collate.hip": [os.path.join(_HERE, "..", "include", "tfgx_collate.h")]}
@@ -218,7 +221,7 @@ def build_asan(force=False, verbose=True):
     os.makedirs(ASAN_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC, x) for x in SOURCES]
     deps = srcs + [os.path.join(CSRC, "tfgx_common.h"), os.path.join(CSRC, "tfgx_sample_rows.h"),
-                   os.path.join(_HERE, "..", "include", "tfgx.h")]
+                   os.path.join(CSRC, "tfgx_host.h"), os.path.join(_HERE, "..", "include", "tfgx.h")]
     if not force and os.path.exists(ASAN_LIB) and not any(_newer(d, ASAN_LIB) for d in deps):
         return ASAN_LIB
     flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",

@@ -15,6 +15,7 @@
 // 64-bit keys, a thread per run head sums its run in order, an exclusive scan of the keep flags places the survivors, and
 // the row pointer is read off the compacted rows.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "../../include/tfgx_asap.h"
 #include <hipcub/hipcub.hpp>
 
@@ -172,7 +173,6 @@ __global__ void __launch_bounds__(kBlock) asap_attend_backward_kernel(const int3
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // S^T A S
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 __global__ void spasp_row_degree(const int32_t* __restrict__ s_row_ptr, const int32_t* __restrict__ s_col, int64_t N, int32_t K,
                                  int32_t* __restrict__ s_deg)
@@ -309,9 +309,9 @@ CountLayout count_layout(int64_t E)
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, out, static_cast<int>(E + 1));
     CountLayout L;
     size_t o = 0;
-    L.cnt = o, o += align_up(8 * size_t(E + 1));
+    L.cnt = o, o += align256(8 * size_t(E + 1));
     L.bad = o, o += 256;
-    L.temp = o, o += align_up(t) + 256;
+    L.temp = o, o += align256(t) + 256;
     L.total = o;
     return L;
 }
@@ -334,13 +334,13 @@ SpaspLayout spasp_layout(int64_t total)
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t2, f, fo, static_cast<int>(n));
     SpaspLayout L;
     size_t o = 0;
-    L.keys = o, o += align_up(8 * n);
-    L.keys_s = o, o += align_up(8 * n);
-    L.vals = o, o += align_up(4 * n);      // the products; after the sort, the run sums
-    L.vals_s = o, o += align_up(4 * n);
-    L.keep = o, o += align_up(4 * n);
-    L.place = o, o += align_up(4 * n);
-    L.temp = o, o += align_up(t1 > t2 ? t1 : t2) + 256;
+    L.keys = o, o += align256(8 * n);
+    L.keys_s = o, o += align256(8 * n);
+    L.vals = o, o += align256(4 * n);      // the products; after the sort, the run sums
+    L.vals_s = o, o += align256(4 * n);
+    L.keep = o, o += align256(4 * n);
+    L.place = o, o += align256(4 * n);
+    L.temp = o, o += align256(t1 > t2 ? t1 : t2) + 256;
     L.total = o;
     return L;
 }

@@ -14,6 +14,7 @@
 // with one 16-byte read from a table of E / 4 bytes instead of a gather from an E-sized rank array.  Rows are never
 // walked: a row of one edge and a hub of a million take the same path.  Integer atomicOr on the bad-index flag only.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "../../include/tfgx_dropedge.h"
 #include <hipcub/hipcub.hpp>
 
@@ -26,7 +27,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 
 enum { kEdges = 0, kUpperEdges = 1, kCsr = 2 };
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 inline int64_t num_tiles(int64_t E) { return (E + kTile - 1) / kTile; }
 inline int64_t num_groups(int64_t E) { return (E + kWave - 1) / kWave; }
 
@@ -188,9 +188,9 @@ Layout layout(int64_t E, int with_any_plan)
     const int32_t* in = nullptr;
     int32_t* out = nullptr;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, in, out, static_cast<int>(L.nt + 1));
-    L.temp_bytes = align_up(scan);
-    const size_t tiles = align_up(sizeof(int32_t) * size_t(L.nt + 2));
-    const size_t table = with_any_plan ? align_up(sizeof(int4) * size_t(L.ng > 0 ? L.ng : 1)) : 0;
+    L.temp_bytes = align256(scan);
+    const size_t tiles = align256(sizeof(int32_t) * size_t(L.nt + 2));
+    const size_t table = with_any_plan ? align256(sizeof(int4) * size_t(L.ng > 0 ? L.ng : 1)) : 0;
     L.off_tile_cnt = 0;
     L.off_tile_off = tiles;
     L.off_etab = 2 * tiles;
@@ -201,8 +201,6 @@ Layout layout(int64_t E, int with_any_plan)
     L.total = L.off_temp + L.temp_bytes;
     return L;
 }
-
-constexpr int64_t kMaxSize = (int64_t(1) << 31) - 1;
 
 int check_common(const char* fn, const int32_t* row, const int32_t* col, int64_t E, int64_t n_dst, int64_t n_src, float rate,
                  int32_t force_undirected)

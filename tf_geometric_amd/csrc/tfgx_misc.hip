@@ -146,47 +146,8 @@ __global__ void split_by_class_kernel(const int32_t* __restrict__ row_ptr, const
 }
 
 // ---- neighbour sampling (RandomNeighborSampler.sample, tf_geometric/utils/graph_utils.py:667-772) ----------
-// the generator and the per-row bodies live in tfgx_sample_rows.h, shared with the row-list sampler of tfgx_nbrblock.hip
-
-// one thread per destination row; out row r holds cnt[r] = out_ptr[r+1]-out_ptr[r] sampled CSR positions' (col, w)
-__global__ void sample_neighbors_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                        const float* __restrict__ w, int64_t n_dst,
-                                        const int32_t* __restrict__ out_ptr, int replace_when_short, uint64_t seed,
-                                        int32_t* __restrict__ out_col, float* __restrict__ out_w)
-{
-    int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; r < n_dst; r += stride) {
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        const int o = out_ptr[r], m = out_ptr[r + 1] - o;
-        if (m == 0) continue;
-        if (sample_row_is_long(d, m)) continue;                   // hub rows: sample_neighbors_long_kernel, a wave each
-        sample_row_lane(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w);
-    }
-}
-
-// Rows with more than 64 neighbours or draws (all of a power-law graph's mass; hubs of 10^4 .. 10^5 neighbours): one WAVE
-// per row instead of one lane — coalesced walks, no divergence between a hub and its wave-mates (R-MAT, ratio = 0.5:
-// 43 ms -> see profiles/r02_skew_cliff_scan.jsonl).  The stratified draw is sample_row_wave (tfgx_sample_rows.h).
-__global__ __launch_bounds__(kBlock) void sample_neighbors_long_kernel(const int32_t* __restrict__ row_ptr,
-                                                                       const int32_t* __restrict__ col,
-                                                                       const float* __restrict__ w, int64_t n_dst,
-                                                                       const int32_t* __restrict__ out_ptr,
-                                                                       int replace_when_short, uint64_t seed,
-                                                                       int32_t* __restrict__ out_col,
-                                                                       float* __restrict__ out_w)
-{
-    constexpr int WV = 64;
-    const int lane = threadIdx.x % WV;
-    int64_t r = (blockIdx.x * int64_t(kBlock) + threadIdx.x) / WV;
-    const int64_t stride = int64_t(gridDim.x) * kBlock / WV;
-    for (; r < n_dst; r += stride) {
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        const int o = out_ptr[r], m = out_ptr[r + 1] - o;
-        if (m == 0 || !sample_row_is_long(d, m)) continue;
-        sample_row_wave(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w, lane);
-    }
-}
+// the generator, the per-row bodies, the kernel pair and its launcher live in tfgx_sample_rows.h, shared with the row-list
+// sampler of tfgx_nbrblock.hip; tfgx_sample_neighbors is their GraphRows instance (row r of the graph -> out row r)
 
 // one pass: x[n, F] -> main[n, f_main] (128-byte aligned rows) + tail[n, F - f_main]
 __global__ __launch_bounds__(kBlock) void split_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int F,
@@ -436,15 +397,8 @@ extern "C" int tfgx_sample_neighbors(const int32_t* row_ptr, const int32_t* col,
     // branch, keep-all rows need no scratch at all
     if (n_dst == 0) return TFGX_OK;
     TFGX_REQUIRE(row_ptr && out_ptr, "null pointer");
-    sample_neighbors_kernel<<<grid_for(n_dst, kBlock), kBlock, 0, as_stream(stream)>>>(
-        row_ptr, col, w, n_dst, out_ptr, replace_when_short, seed, out_col, out_w);
-    TFGX_LAUNCH_CHECK("sample_neighbors_kernel");
-    // rows the lane-per-row kernel skipped (hubs): a wave each; a pass over row_ptr / out_ptr when there are none
-    // (an ODD grid: with a power-of-two row stride the hubs of an R-MAT graph — ids k * 2^16 — would all land in one wave)
-    sample_neighbors_long_kernel<<<grid_for(n_dst * 64, kBlock, (1 << 14) - 3), kBlock, 0, as_stream(stream)>>>(
-        row_ptr, col, w, n_dst, out_ptr, replace_when_short, seed, out_col, out_w);
-    TFGX_LAUNCH_CHECK("sample_neighbors_long_kernel");
-    return TFGX_OK;
+    return launch_sample_rows(row_ptr, col, w, GraphRows{seed}, n_dst, out_ptr, replace_when_short, out_col, out_w,
+                              as_stream(stream));
 }
 
 extern "C" int tfgx_split_by_source_class(const int32_t* row_ptr, const int32_t* col_local, const float* w,

@@ -3,8 +3,8 @@
 //
 // Reference: tf_geometric/utils/graph_utils.py:630-772 (RandomNeighborSampler), demo/demo_graph_sage.py (a block per layer).
 //
-// The sampler runs the per-row bodies of tfgx_sample_rows.h (the ones tfgx_sample_neighbors runs) with the generator keyed by
-// the GLOBAL node id rows[i] and the output offset out_ptr[i]: same bits as the whole-graph sampler, row by row.
+// The sampler is the ListedRows instance of tfgx_sample_rows.h's kernel pair (tfgx_sample_neighbors is another): the generator
+// keyed by the GLOBAL node id rows[i], the output offset out_ptr[i] — same bits as the whole-graph sampler, row by row.
 //
 // The relabel is four launches over the E sampled ids with a kernel boundary between any two that hand data on (nothing is
 // passed between workgroups inside a launch):
@@ -15,62 +15,14 @@
 //             to node_list; the last position writes *n_new.  The table is only read.
 //   settle  : a first occurrence replaces its table entry by the virtual id (plain store, one writer per entry).
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "tfgx_sample_rows.h"
 #include "../../include/tfgx_nbrblock.h"
-#include <hipcub/hipcub.hpp>
 
 namespace tfgx {
 namespace {
 
-constexpr int64_t kMaxSize = (int64_t(1) << 31) - 1;
 constexpr int32_t kEmpty = TFGX_NBRBLOCK_EMPTY;
-
-// one lane per listed row; rows[i] is compared with [0, n_nodes) before anything is indexed by it
-__global__ void sample_rows_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                   const float* __restrict__ w, int32_t n_nodes, const int32_t* __restrict__ rows,
-                                   int64_t n_rows, const int32_t* __restrict__ out_ptr, int replace_when_short, uint64_t seed,
-                                   int32_t* __restrict__ out_col, float* __restrict__ out_w, int32_t* __restrict__ bad_flag)
-{
-    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; i < n_rows; i += stride) {
-        const int32_t r = rows[i];
-        if (r < 0 || r >= n_nodes) {
-            atomicOr(bad_flag, TFGX_NBRBLOCK_BAD_RANGE);
-            continue;
-        }
-        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
-        if (m <= 0) continue;
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        if (d <= 0) continue;                                     // draws asked of a node without neighbours: nothing to read
-        if (sample_row_is_long(d, m)) continue;                   // sample_rows_long_kernel, a wave each
-        sample_row_lane(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w);
-    }
-}
-
-// the long rows of the list, a wave each (the range refusal is the lane kernel's)
-__global__ __launch_bounds__(kBlock) void sample_rows_long_kernel(const int32_t* __restrict__ row_ptr,
-                                                                  const int32_t* __restrict__ col,
-                                                                  const float* __restrict__ w, int32_t n_nodes,
-                                                                  const int32_t* __restrict__ rows, int64_t n_rows,
-                                                                  const int32_t* __restrict__ out_ptr, int replace_when_short,
-                                                                  uint64_t seed, int32_t* __restrict__ out_col,
-                                                                  float* __restrict__ out_w)
-{
-    constexpr int WV = 64;
-    const int lane = threadIdx.x % WV;
-    int64_t i = (blockIdx.x * int64_t(kBlock) + threadIdx.x) / WV;
-    const int64_t stride = int64_t(gridDim.x) * kBlock / WV;
-    for (; i < n_rows; i += stride) {
-        const int32_t r = rows[i];
-        if (r < 0 || r >= n_nodes) continue;
-        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
-        if (m <= 0) continue;
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        if (d <= 0 || !sample_row_is_long(d, m)) continue;
-        sample_row_wave(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w, lane);
-    }
-}
 
 __global__ void stamp_kernel(int32_t* __restrict__ table, int32_t n_nodes, const int32_t* __restrict__ ids, int64_t n,
                              int32_t base, int32_t* __restrict__ flag)
@@ -156,35 +108,10 @@ __global__ void reset_kernel(int32_t* __restrict__ table, int32_t n_nodes, const
     }
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-size_t scan_bytes(int64_t E)
+// the relabel's workspace: first [E], rank [E], the scan's scratch
+Workspace<3> relabel_workspace(int64_t E)
 {
-    size_t temp = 0;
-    const int32_t* in = nullptr;
-    int32_t* out = nullptr;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, temp, in, out, static_cast<int>(E > 0 ? E : 1));
-    return temp;
-}
-
-// the refusals every entry point shares: a negative size, a size that does not fit int32 — with the argument named
-int check_size(const char* fn, const char* name, int64_t v)
-{
-    if (v < 0) {
-        set_error("%s: negative size (%s = %lld)", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (v >= kMaxSize) {
-        set_error("%s: %s = %lld does not fit int32", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    return TFGX_OK;
-}
-
-int null_arg(const char* fn, const char* name)
-{
-    set_error("%s: %s is null", fn, name);
-    return TFGX_ERR_INVALID_ARG;
+    return {{sizeof(int32_t) * size_t(E), sizeof(int32_t) * size_t(E), scan_bytes(E)}};
 }
 
 }  // namespace
@@ -209,15 +136,8 @@ extern "C" int tfgx_nbrblock_sample_rows(const int32_t* row_ptr, const int32_t* 
     if (n_nodes > 0 && row_ptr == nullptr) return null_arg(__func__, "row_ptr");
     if (n_nodes > 0 && col == nullptr) return null_arg(__func__, "col");
     if (n_nodes > 0 && out_col == nullptr) return null_arg(__func__, "out_col");
-    sample_rows_kernel<<<grid_for(n_rows, kBlock), kBlock, 0, as_stream(stream)>>>(
-        row_ptr, col, w, int32_t(n_nodes), rows, n_rows, out_ptr, replace_when_short, seed, out_col, out_w, bad_flag);
-    TFGX_LAUNCH_CHECK("sample_rows_kernel");
-    // the rows the lane kernel left (hubs): a wave each; a pass over rows / out_ptr when there are none.  The grid is sized by
-    // n_rows (an odd cap, as tfgx_sample_neighbors: ids k * 2^16 of an R-MAT graph's hubs must not share a wave slot)
-    sample_rows_long_kernel<<<grid_for(n_rows * 64, kBlock, (1 << 14) - 3), kBlock, 0, as_stream(stream)>>>(
-        row_ptr, col, w, int32_t(n_nodes), rows, n_rows, out_ptr, replace_when_short, seed, out_col, out_w);
-    TFGX_LAUNCH_CHECK("sample_rows_long_kernel");
-    return TFGX_OK;
+    const ListedRows listed{rows, int32_t(n_nodes), bad_flag, TFGX_NBRBLOCK_BAD_RANGE, seed};
+    return launch_sample_rows(row_ptr, col, w, listed, n_rows, out_ptr, replace_when_short, out_col, out_w, as_stream(stream));
 }
 
 extern "C" int tfgx_nbrblock_stamp(int32_t* table, int64_t n_nodes, const int32_t* ids, int64_t n, int64_t base, int32_t* flag,
@@ -243,7 +163,7 @@ extern "C" int tfgx_nbrblock_stamp(int32_t* table, int64_t n_nodes, const int32_
 extern "C" size_t tfgx_nbrblock_relabel_workspace_bytes(int64_t E)
 {
     if (E <= 0 || E >= kMaxSize) return 0;
-    return 2 * align256(sizeof(int32_t) * size_t(E)) + align256(scan_bytes(E)) + 256;
+    return relabel_workspace(E).bytes();
 }
 
 extern "C" int tfgx_nbrblock_relabel(int32_t* table, int64_t n_nodes, int64_t n_known, const int32_t* cols, int64_t E,
@@ -271,12 +191,11 @@ extern "C" int tfgx_nbrblock_relabel(int32_t* table, int64_t n_nodes, int64_t n_
                   workspace_bytes, tfgx_nbrblock_relabel_workspace_bytes(E));
         return TFGX_ERR_WORKSPACE;
     }
-    // carve: first [E], rank [E], the scan's scratch — each on a 256-byte boundary of the caller's block
-    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
-    int32_t* first = reinterpret_cast<int32_t*>(base);
-    int32_t* rank = reinterpret_cast<int32_t*>(base + align256(sizeof(int32_t) * size_t(E)));
-    void* temp = base + 2 * align256(sizeof(int32_t) * size_t(E));
-    size_t temp_bytes = scan_bytes(E);
+    const Workspace<3> ws = relabel_workspace(E);
+    int32_t* first = ws.at<int32_t>(workspace, 0);
+    int32_t* rank = ws.at<int32_t>(workspace, 1);
+    void* temp = ws.at(workspace, 2);
+    size_t temp_bytes = ws.piece[2];
 
     const int grid = grid_for(E, kBlock);
     relabel_mark_kernel<<<grid, kBlock, 0, stream>>>(table, int32_t(n_nodes), int32_t(n_known), cols, E);

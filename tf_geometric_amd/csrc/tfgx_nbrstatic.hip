@@ -8,8 +8,8 @@
 //   count   : cnt[i] = draws of row i from row_ptr[node[i]], 0 for a dead row (and for the extra entry R); the candidate id
 //             list is filled with -1 (what the relabel skips).
 //   scan    : ONE exclusive sum cnt -> block_row_ptr[0 .. R]; block_row_ptr[R] is the hop's edge total.
-//   sample  : the per-row bodies of tfgx_sample_rows.h (the ones tfgx_nbrblock_sample_rows runs: a lane per short row, a wave
-//             per long one, the same sample_row_is_long split), keyed by the global id, the seed mixed from the device word.
+//   sample  : the kernel pair of tfgx_sample_rows.h (the one tfgx_nbrblock_sample_rows launches: a lane per short row, a wave
+//             per long one), its ListedRowsDeviceSeed instance: keyed by the global id, the seed mixed from the device word.
 //   relabel : tfgx_nbrblock_relabel over the E candidate slots with n_known = R: new ids take R, R + 1, ... in first-occurrence
 //             order (integer atomicMin, flags, a scan), their global ids land in node[R ...], counts[1] = how many.
 //   finish  : row positions of the sampled edges (a binary search in block_row_ptr), the tail self-loops on the sinks with unit
@@ -17,15 +17,13 @@
 // The other entry of the header, tfgx_nbrstatic_input_hop_f32, is the seed-pointer form of samplereduce_kernel and lives in
 // tfgx_samplereduce.hip.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "tfgx_sample_rows.h"
 #include "../../include/tfgx_nbrblock.h"
 #include "../../include/tfgx_nbrstatic.h"
-#include <hipcub/hipcub.hpp>
 
 namespace tfgx {
 namespace {
-
-constexpr int64_t kMaxSize = (int64_t(1) << 31) - 1;
 
 __global__ void seeds_mark_kernel(int32_t* __restrict__ table, int32_t n_nodes, const int32_t* __restrict__ seeds, int64_t B,
                                   int32_t* __restrict__ flag)
@@ -70,59 +68,11 @@ __global__ void hop_count_kernel(const int32_t* __restrict__ row_ptr, int32_t n_
         int m = 0;
         if (i < R) {
             const int32_t r = node[i];
-            if (r >= 0 && r < n_nodes) {
-                const int d = row_ptr[r + 1] - row_ptr[r];
-                m = d <= 0 ? 0 : (replace_when_short ? k : min(d, k));
-            }
+            if (r >= 0 && r < n_nodes) m = sample_row_draws(row_ptr[r + 1] - row_ptr[r], k, replace_when_short);
         }
         cnt[i] = m;
     }
     for (int64_t p = t0; p < E; p += stride) gcol[p] = -1;
-}
-
-// one lane per row; a dead row (and an id the sampler cannot have produced) is passed over
-__global__ void hop_sample_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                  const float* __restrict__ w, int32_t n_nodes, const int32_t* __restrict__ node, int64_t R,
-                                  const int32_t* __restrict__ out_ptr, int replace_when_short,
-                                  const uint64_t* __restrict__ seed_dev, int hop, int32_t* __restrict__ out_col,
-                                  float* __restrict__ out_w)
-{
-    const uint64_t seed = hop_seed_from(seed_dev, hop);
-    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; i < R; i += stride) {
-        const int32_t r = node[i];
-        if (r < 0 || r >= n_nodes) continue;
-        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
-        if (m <= 0) continue;
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        if (d <= 0) continue;
-        if (sample_row_is_long(d, m)) continue;                   // hop_sample_long_kernel, a wave each
-        sample_row_lane(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void hop_sample_long_kernel(const int32_t* __restrict__ row_ptr,
-                                                                 const int32_t* __restrict__ col, const float* __restrict__ w,
-                                                                 int32_t n_nodes, const int32_t* __restrict__ node, int64_t R,
-                                                                 const int32_t* __restrict__ out_ptr, int replace_when_short,
-                                                                 const uint64_t* __restrict__ seed_dev, int hop,
-                                                                 int32_t* __restrict__ out_col, float* __restrict__ out_w)
-{
-    constexpr int WV = 64;
-    const uint64_t seed = hop_seed_from(seed_dev, hop);
-    const int lane = threadIdx.x % WV;
-    int64_t i = (blockIdx.x * int64_t(kBlock) + threadIdx.x) / WV;
-    const int64_t stride = int64_t(gridDim.x) * kBlock / WV;
-    for (; i < R; i += stride) {
-        const int32_t r = node[i];
-        if (r < 0 || r >= n_nodes) continue;
-        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
-        if (m <= 0) continue;
-        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
-        if (d <= 0 || !sample_row_is_long(d, m)) continue;
-        sample_row_wave(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w, lane);
-    }
 }
 
 // after the relabel: block_col[0 .. total) and node[R .. R + n_new) are written, counts[1] = n_new
@@ -211,24 +161,6 @@ __global__ void gather_rows_kernel(const float* __restrict__ x, int64_t ldx, con
     }
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-size_t scan_bytes(int64_t n)
-{
-    size_t temp = 0;
-    const int32_t* in = nullptr;
-    int32_t* out = nullptr;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, temp, in, out, static_cast<int>(n > 0 ? n : 1));
-    return temp;
-}
-
-int key_bits(int64_t n)
-{
-    int b = 1;
-    while (b < 31 && (int64_t(1) << b) < n) ++b;
-    return b;
-}
-
 size_t sort_bytes(int64_t E, int64_t n)
 {
     size_t temp = 0;
@@ -238,37 +170,25 @@ size_t sort_bytes(int64_t E, int64_t n)
     return temp;
 }
 
-int check_size(const char* fn, const char* name, int64_t v)
-{
-    if (v < 0) {
-        set_error("%s: negative size (%s = %lld)", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (v >= kMaxSize) {
-        set_error("%s: %s = %lld does not fit int32", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    return TFGX_OK;
-}
-
-int null_arg(const char* fn, const char* name)
-{
-    set_error("%s: %s is null", fn, name);
-    return TFGX_ERR_INVALID_ARG;
-}
-
-int bad_arg(const char* fn, const char* what, long long v)
-{
-    set_error("%s: %s (got %lld)", fn, what, v);
-    return TFGX_ERR_INVALID_ARG;
-}
-
 // R' = R + R * k + (k > 0 ? R : 0), or -1 when it does not fit int32
 int64_t hop_nodes(int64_t R, int32_t k)
 {
     if (R < 0 || k < 0 || R >= kMaxSize) return -1;
     const int64_t total = R + R * int64_t(k) + (k > 0 ? R : 0);       // R < 2^31, k < 2^31: no int64 overflow
     return total >= kMaxSize ? -1 : total;
+}
+
+// a hop's workspace: cnt [R + 1], the candidate ids [E], the scan's scratch, the relabel's
+Workspace<4> hop_workspace(int64_t R, int64_t E)
+{
+    return {{sizeof(int32_t) * size_t(R + 1), sizeof(int32_t) * size_t(E), scan_bytes(R + 1),
+             tfgx_nbrblock_relabel_workspace_bytes(E)}};
+}
+
+// the transpose's workspace: the sorted keys [E], the positions [E], hipcub's own
+Workspace<3> transpose_workspace(int64_t E, int64_t n)
+{
+    return {{sizeof(int32_t) * size_t(E), sizeof(int32_t) * size_t(E), sort_bytes(E, n)}};
 }
 
 }  // namespace
@@ -300,10 +220,7 @@ extern "C" int tfgx_nbrstatic_seeds(int32_t* table, int64_t n_nodes, const int32
 extern "C" size_t tfgx_nbrstatic_hop_workspace_bytes(int64_t R, int32_t k)
 {
     if (R <= 0 || k <= 0 || hop_nodes(R, k) < 0) return 0;
-    const int64_t E = R * int64_t(k);
-    // cnt [R + 1], the candidate ids [E], the scan's own, the relabel's
-    return align256(sizeof(int32_t) * size_t(R + 1)) + align256(sizeof(int32_t) * size_t(E)) + align256(scan_bytes(R + 1)) +
-           align256(tfgx_nbrblock_relabel_workspace_bytes(E)) + 256;
+    return hop_workspace(R, R * int64_t(k)).bytes();
 }
 
 extern "C" int tfgx_nbrstatic_hop(const int32_t* row_ptr, const int32_t* col, const float* w, int64_t n_nodes, int32_t* table,
@@ -345,30 +262,21 @@ extern "C" int tfgx_nbrstatic_hop(const int32_t* row_ptr, const int32_t* col, co
                   workspace_bytes, tfgx_nbrstatic_hop_workspace_bytes(R, k));
         return TFGX_ERR_WORKSPACE;
     }
-    // carve: cnt [R + 1], gcol [E], the scan's scratch, the relabel's — each on a 256-byte boundary of the caller's block
-    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
-    int32_t* cnt = reinterpret_cast<int32_t*>(base);
-    base += align256(sizeof(int32_t) * size_t(R + 1));
-    int32_t* gcol = reinterpret_cast<int32_t*>(base);
-    base += align256(sizeof(int32_t) * size_t(E));
-    void* scan_temp = base;
-    size_t scan_temp_bytes = scan_bytes(R + 1);
-    base += align256(scan_temp_bytes);
-    void* relabel_ws = base;
-    const size_t relabel_bytes = tfgx_nbrblock_relabel_workspace_bytes(E);
+    const Workspace<4> ws = hop_workspace(R, E);
+    int32_t* cnt = ws.at<int32_t>(workspace, 0);
+    int32_t* gcol = ws.at<int32_t>(workspace, 1);
+    void* scan_temp = ws.at(workspace, 2);
+    size_t scan_temp_bytes = ws.piece[2];
+    void* relabel_ws = ws.at(workspace, 3);
+    const size_t relabel_bytes = ws.piece[3];
 
     hop_count_kernel<<<grid_for(E > R ? E : R + 1, kBlock), kBlock, 0, stream>>>(row_ptr, int32_t(n_nodes), node, R, k,
                                                                                  replace_when_short, E, cnt, gcol);
     TFGX_LAUNCH_CHECK("hop_count_kernel");
     TFGX_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, cnt, block_row_ptr, static_cast<int>(R + 1),
                                                     stream));
-    hop_sample_kernel<<<grid_for(R, kBlock), kBlock, 0, stream>>>(row_ptr, col, w, int32_t(n_nodes), node, R, block_row_ptr,
-                                                                  replace_when_short, seed, hop, gcol, block_w);
-    TFGX_LAUNCH_CHECK("hop_sample_kernel");
-    // (an odd cap, as tfgx_nbrblock_sample_rows: ids k * 2^16 of an R-MAT graph's hubs must not share a wave slot)
-    hop_sample_long_kernel<<<grid_for(R * 64, kBlock, (1 << 14) - 3), kBlock, 0, stream>>>(
-        row_ptr, col, w, int32_t(n_nodes), node, R, block_row_ptr, replace_when_short, seed, hop, gcol, block_w);
-    TFGX_LAUNCH_CHECK("hop_sample_long_kernel");
+    const ListedRowsDeviceSeed listed{node, int32_t(n_nodes), seed, hop};
+    if (int rc = launch_sample_rows(row_ptr, col, w, listed, R, block_row_ptr, replace_when_short, gcol, block_w, stream)) return rc;
     // new ids are numbered R, R + 1, ... and appended to node[R ...]; the slots past the total hold -1 and are skipped
     if (int rc = tfgx_nbrblock_relabel(table, n_nodes, R, gcol, E, block_col, node, counts + 1, relabel_ws, relabel_bytes,
                                        stream_))
@@ -382,8 +290,7 @@ extern "C" int tfgx_nbrstatic_hop(const int32_t* row_ptr, const int32_t* col, co
 extern "C" size_t tfgx_nbrstatic_transpose_workspace_bytes(int64_t E, int64_t n)
 {
     if (E <= 0 || n < 0 || E >= kMaxSize || n >= kMaxSize) return 0;
-    // the sorted keys [E], the positions [E], hipcub's own
-    return 2 * align256(sizeof(int32_t) * size_t(E)) + align256(sort_bytes(E, n)) + 256;
+    return transpose_workspace(E, n).bytes();
 }
 
 extern "C" int tfgx_nbrstatic_transpose(const int32_t* block_row, const int32_t* block_col, int64_t E, int64_t n,
@@ -411,11 +318,11 @@ extern "C" int tfgx_nbrstatic_transpose(const int32_t* block_row, const int32_t*
                   workspace_bytes, tfgx_nbrstatic_transpose_workspace_bytes(E, n));
         return TFGX_ERR_WORKSPACE;
     }
-    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
-    int32_t* keys_out = reinterpret_cast<int32_t*>(base);
-    int32_t* iota = reinterpret_cast<int32_t*>(base + align256(sizeof(int32_t) * size_t(E)));
-    void* temp = base + 2 * align256(sizeof(int32_t) * size_t(E));
-    size_t temp_bytes = sort_bytes(E, n);
+    const Workspace<3> ws = transpose_workspace(E, n);
+    int32_t* keys_out = ws.at<int32_t>(workspace, 0);
+    int32_t* iota = ws.at<int32_t>(workspace, 1);
+    void* temp = ws.at(workspace, 2);
+    size_t temp_bytes = ws.piece[2];
 
     const int grid = grid_for(E, kBlock);
     iota_kernel<<<grid, kBlock, 0, stream>>>(E, iota);

@@ -5,6 +5,7 @@
 // per graph: a stable LSD radix sort of (row, edge id) (hipcub::DeviceRadixSort, plumbing only),
 // then row_ptr from the sorted keys' boundaries (no atomics, no scan).
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include <hipcub/hipcub.hpp>
 #include <dlfcn.h>
 #include <cstdlib>
@@ -58,15 +59,6 @@ void set_error(const char* fmt, ...)
 }
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-inline int key_bits(int64_t n)
-{
-    int b = 1;
-    while (b < 31 && (int64_t(1) << b) < n) ++b;
-    return b;
-}
 
 __global__ void validate_and_iota(const int32_t* __restrict__ row, const int32_t* __restrict__ col, int64_t E,
                                   int32_t n_dst, int32_t n_src, int32_t* __restrict__ iota,
@@ -188,7 +180,7 @@ extern "C" size_t tfgx_csr_plan_workspace_bytes(int64_t n_dst, int64_t E)
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, temp, kin, kout, kin, kout, static_cast<int>(E > 0 ? E : 1), 0,
                                        key_bits(n_dst));
     // [bad flag | keys_out | iota | hipcub temp]
-    return 256 + 2 * align_up(sizeof(int32_t) * size_t(E > 0 ? E : 1)) + align_up(temp) + 256;
+    return 256 + 2 * align256(sizeof(int32_t) * size_t(E > 0 ? E : 1)) + align256(temp) + 256;
 }
 
 extern "C" int tfgx_build_csr_by_dst(const int32_t* row, const int32_t* col, int64_t E, int64_t n_dst,
@@ -214,9 +206,9 @@ extern "C" int tfgx_build_csr_by_dst(const int32_t* row, const int32_t* col, int
     char* ws = static_cast<char*>(workspace);
     int32_t* bad = reinterpret_cast<int32_t*>(ws);
     int32_t* keys_out = reinterpret_cast<int32_t*>(ws + 256);
-    int32_t* iota = reinterpret_cast<int32_t*>(ws + 256 + align_up(sizeof(int32_t) * size_t(E)));
-    void* temp = ws + 256 + 2 * align_up(sizeof(int32_t) * size_t(E));
-    size_t temp_bytes = workspace_bytes - (256 + 2 * align_up(sizeof(int32_t) * size_t(E)));
+    int32_t* iota = reinterpret_cast<int32_t*>(ws + 256 + align256(sizeof(int32_t) * size_t(E)));
+    void* temp = ws + 256 + 2 * align256(sizeof(int32_t) * size_t(E));
+    size_t temp_bytes = workspace_bytes - (256 + 2 * align256(sizeof(int32_t) * size_t(E)));
 
     TFGX_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), stream));
     validate_and_iota<<<grid_for(E, kBlock), kBlock, 0, stream>>>(row, col, E, int32_t(n_dst), int32_t(n_src),
@@ -268,8 +260,8 @@ extern "C" size_t tfgx_merge_edges_workspace_bytes(int64_t E, int64_t n)
     int32_t* vo = nullptr;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k, ko, v, vo, static_cast<int>(E), 0, hash_bits(n));
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, t2, v, vo, static_cast<int>(E));
-    const size_t a8 = align_up(sizeof(int64_t) * size_t(E)), a4 = align_up(sizeof(int32_t) * size_t(E));
-    return 2 * a8 + 7 * a4 + align_up(t1 > t2 ? t1 : t2) + 256;
+    const size_t a8 = align256(sizeof(int64_t) * size_t(E)), a4 = align256(sizeof(int32_t) * size_t(E));
+    return 2 * a8 + 7 * a4 + align256(t1 > t2 ? t1 : t2) + 256;
 }
 
 extern "C" int tfgx_merge_duplicated_edges(const int32_t* row, const int32_t* col, int64_t E, int64_t n,
@@ -289,7 +281,7 @@ extern "C" int tfgx_merge_duplicated_edges(const int32_t* row, const int32_t* co
         set_error("tfgx_merge_duplicated_edges: workspace too small");
         return TFGX_ERR_WORKSPACE;
     }
-    const size_t a8 = align_up(sizeof(int64_t) * size_t(E)), a4 = align_up(sizeof(int32_t) * size_t(E));
+    const size_t a8 = align256(sizeof(int64_t) * size_t(E)), a4 = align256(sizeof(int32_t) * size_t(E));
     char* ws = static_cast<char*>(workspace);
     int64_t* keys = reinterpret_cast<int64_t*>(ws);
     int64_t* keys_s = reinterpret_cast<int64_t*>(ws + a8);

@@ -14,6 +14,7 @@
 //                   col_k written once, rpk once.
 // Integer atomics only (the degree maximum); never on floats.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include <hipcub/hipcub.hpp>
 #include <cmath>
 
@@ -22,8 +23,6 @@ namespace {
 
 constexpr int kWavesPerBlockP = kBlock / kWave;
 constexpr int kMaxSourceBlocks = 64;                    // one lane per block of a row
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 inline int value_bits(int64_t v)
 {
@@ -229,13 +228,13 @@ RowOrderLayout row_order_layout(int64_t n_dst)
     const int32_t* vin = nullptr;
     int32_t* vout = nullptr;
     (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp, kin, kout, vin, vout, n, 0, 31);
-    const size_t a4 = align_up(sizeof(int32_t) * size_t(n));
+    const size_t a4 = align256(sizeof(int32_t) * size_t(n));
     L.off_max = 0;
     L.off_deg = 256;
     L.off_deg_out = L.off_deg + a4;
     L.off_iota = L.off_deg_out + a4;
     L.off_temp = L.off_iota + a4;
-    L.temp_bytes = align_up(temp);
+    L.temp_bytes = align256(temp);
     L.total = L.off_temp + L.temp_bytes;
     return L;
 }
@@ -255,14 +254,14 @@ HubLayout hub_layout(int64_t n)
     int64_t* o64 = nullptr;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t32, i32, o32, static_cast<int>(n + 1));
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t64, i64, o64, static_cast<int>(n + 1));
-    const size_t a4 = align_up(sizeof(int32_t) * size_t(n + 1)), a8 = align_up(sizeof(int64_t) * size_t(n + 1));
+    const size_t a4 = align256(sizeof(int32_t) * size_t(n + 1)), a8 = align256(sizeof(int64_t) * size_t(n + 1));
     L.off_flag = 0;
     L.off_pos = a4;
     L.off_nch = 2 * a4;
     L.off_off = 2 * a4 + a8;
     L.off_totals = 2 * a4 + 2 * a8;
     L.off_temp = L.off_totals + 256;
-    L.temp_bytes = align_up(t32 > t64 ? t32 : t64);
+    L.temp_bytes = align256(t32 > t64 ? t32 : t64);
     L.total = L.off_temp + L.temp_bytes;
     return L;
 }

@@ -24,6 +24,7 @@
 //                         exactly (every tied edge receives g / count)
 //   pool_wgrad_reduce     dW / db = the workgroups' partials added in workgroup order
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 
 namespace tfgx {
 namespace {
@@ -365,8 +366,6 @@ inline size_t pool_lds_bytes(int kmax)
 {
     return size_t(2) * kPoolChunk * size_t(kmax + 4) * sizeof(float) + size_t(2) * kPoolChunk * sizeof(int);
 }
-
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 }  // namespace tfgx

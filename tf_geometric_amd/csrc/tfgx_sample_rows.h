@@ -1,7 +1,9 @@
-// The neighbour sampler's generator and per-row bodies (RandomNeighborSampler.sample, tf_geometric/utils/graph_utils.py:667-772),
-// shared by the whole-graph sampler (tfgx_misc.hip: row r of the graph -> out row r) and the row-list sampler
-// (tfgx_nbrblock.hip: node rows[i] -> out row i).  A body is parameterised by the ROW ID that keys the generator and by the
-// OUTPUT OFFSET of the row; given the same (seed, row id, d, m, replace_when_short) both callers write the same bits.
+// The neighbour sampler (RandomNeighborSampler.sample, tf_geometric/utils/graph_utils.py:667-772): the generator, the per-row
+// bodies, and the ONE kernel pair and launcher that run them for the whole-graph sampler (tfgx_misc.hip: row r of the graph ->
+// out row r), the row-list sampler (tfgx_nbrblock.hip: node rows[i] -> out row i) and the fixed-shape hop (tfgx_nbrstatic.hip:
+// the same, the seed read from the device).  A body is parameterised by the ROW ID that keys the generator and by the OUTPUT
+// OFFSET of the row; given the same (seed, row id, d, m, replace_when_short) every caller writes the same bits.  The fused input
+// hop (tfgx_samplereduce.hip) runs the bodies from its own kernel: its rows are lanes of a tile.
 #pragma once
 #include "tfgx_common.h"
 
@@ -35,6 +37,12 @@ constexpr int kFloydMax = 32;            // Floyd's O(m^2) duplicate check only 
 __device__ __forceinline__ bool sample_row_is_long(int d, int m)
 {
     return (d > kSampleLongRow && m > kFloydMax) || m > kSampleLongRow;
+}
+
+// how many neighbours a row of d draws at fan-out k: none from an empty row, k with replacement, otherwise no more than it has
+__device__ __forceinline__ int sample_row_draws(int d, int k, int replace_when_short)
+{
+    return d <= 0 ? 0 : (replace_when_short ? k : min(d, k));
 }
 
 // ONE LANE samples m > 0 of the d neighbours at CSR positions [s, s + d) of row `r` into out_col / out_w [o, o + m); the row
@@ -125,6 +133,122 @@ __device__ __forceinline__ void sample_row_wave(const int32_t* __restrict__ col,
             ++taken;
         }
     }
+}
+
+// ---- which rows a launch samples: a compile-time ROW SOURCE.  node(i, r, report) gives the node r whose neighbours output row i
+// draws — r indexes row_ptr and keys the generator — or false for a row to pass over; seed() is the launch's seed; kListed says
+// that the rows are a caller's list of ids (sample_row_is_empty).
+struct GraphRows {                       // row i is node i of the graph: nothing to look up, nothing to refuse
+    static constexpr bool kListed = false;
+    uint64_t seed_;
+    __device__ __forceinline__ bool node(int64_t i, int64_t& r, bool) const
+    {
+        r = i;
+        return true;
+    }
+    __device__ __forceinline__ uint64_t seed() const { return seed_; }
+};
+
+struct ListedRows {                      // node ids[i], refused against [0, n_nodes) before anything is indexed by it: the lane
+    static constexpr bool kListed = true;        // kernel (report) ORs flag_bit into *flag, the wave kernel passes over silently
+    const int32_t* ids;
+    int32_t n_nodes;
+    int32_t* flag;
+    int32_t flag_bit;
+    uint64_t seed_;
+    __device__ __forceinline__ bool node(int64_t i, int64_t& r, bool report) const
+    {
+        r = ids[i];
+        if (r >= 0 && r < n_nodes) return true;
+        if (report) atomicOr(flag, flag_bit);
+        return false;
+    }
+    __device__ __forceinline__ uint64_t seed() const { return seed_; }
+};
+
+struct ListedRowsDeviceSeed {            // node ids[i]; a dead row (and an id the sampler cannot have produced) is passed over
+    static constexpr bool kListed = true;        // with no flag; the seed is hop `hop`'s mix of the device word
+    const int32_t* ids;
+    int32_t n_nodes;
+    const uint64_t* seed_dev;
+    int hop;
+    __device__ __forceinline__ bool node(int64_t i, int64_t& r, bool) const
+    {
+        r = ids[i];
+        return r >= 0 && r < n_nodes;
+    }
+    __device__ __forceinline__ uint64_t seed() const { return hop_seed_from(seed_dev, hop); }
+};
+
+// a row that draws nothing.  The whole graph's out_ptr follows its row_ptr: only m == 0 is met.  In a list, draws may have been
+// asked of a node without neighbours (d <= 0): nothing to read
+template <class Rows>
+__device__ __forceinline__ bool sample_row_is_empty(int d, int m)
+{
+    return Rows::kListed ? (m <= 0 || d <= 0) : m == 0;
+}
+
+// one lane per row: out row i holds out_ptr[i + 1] - out_ptr[i] sampled CSR positions' (col, w)
+template <class Rows>
+__global__ void sample_lane_per_row_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                           const float* __restrict__ w, int64_t n_rows,
+                                           const int32_t* __restrict__ out_ptr, int replace_when_short, Rows rows,
+                                           int32_t* __restrict__ out_col, float* __restrict__ out_w)
+{
+    const uint64_t seed = rows.seed();
+    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (; i < n_rows; i += stride) {
+        int64_t r;
+        if (!rows.node(i, r, true)) continue;
+        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
+        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
+        if (sample_row_is_empty<Rows>(d, m)) continue;
+        if (sample_row_is_long(d, m)) continue;                   // sample_wave_per_row_kernel, a wave each
+        sample_row_lane(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w);
+    }
+}
+
+// Rows with more than 64 neighbours or draws (all of a power-law graph's mass; hubs of 10^4 .. 10^5 neighbours): one WAVE
+// per row instead of one lane — coalesced walks, no divergence between a hub and its wave-mates (R-MAT, ratio = 0.5:
+// 43 ms -> see profiles/r02_skew_cliff_scan.jsonl).  The stratified draw is sample_row_wave.
+template <class Rows>
+__global__ __launch_bounds__(kBlock) void sample_wave_per_row_kernel(const int32_t* __restrict__ row_ptr,
+                                                                     const int32_t* __restrict__ col,
+                                                                     const float* __restrict__ w, int64_t n_rows,
+                                                                     const int32_t* __restrict__ out_ptr,
+                                                                     int replace_when_short, Rows rows,
+                                                                     int32_t* __restrict__ out_col, float* __restrict__ out_w)
+{
+    constexpr int WV = 64;
+    const uint64_t seed = rows.seed();
+    const int lane = threadIdx.x % WV;
+    int64_t i = (blockIdx.x * int64_t(kBlock) + threadIdx.x) / WV;
+    const int64_t stride = int64_t(gridDim.x) * kBlock / WV;
+    for (; i < n_rows; i += stride) {
+        int64_t r;
+        if (!rows.node(i, r, false)) continue;
+        const int s = row_ptr[r], d = row_ptr[r + 1] - s;
+        const int o = out_ptr[i], m = out_ptr[i + 1] - o;
+        if (sample_row_is_empty<Rows>(d, m) || !sample_row_is_long(d, m)) continue;
+        sample_row_wave(col, w, uint64_t(r), s, d, o, m, replace_when_short, seed, out_col, out_w, lane);
+    }
+}
+
+// both launches of a sample on `stream`: a lane per row, then a wave for each row the lanes left (hubs) — a pass over the ids
+// and out_ptr when there are none.  The second grid is capped at an ODD size: with a power-of-two row stride the hubs of an R-MAT
+// graph — ids k * 2^16 — would all land in one wave slot.
+template <class Rows>
+inline int launch_sample_rows(const int32_t* row_ptr, const int32_t* col, const float* w, const Rows& rows, int64_t n_rows,
+                              const int32_t* out_ptr, int replace_when_short, int32_t* out_col, float* out_w, hipStream_t stream)
+{
+    sample_lane_per_row_kernel<<<grid_for(n_rows, kBlock), kBlock, 0, stream>>>(row_ptr, col, w, n_rows, out_ptr,
+                                                                                 replace_when_short, rows, out_col, out_w);
+    TFGX_LAUNCH_CHECK("sample_lane_per_row_kernel");
+    sample_wave_per_row_kernel<<<grid_for(n_rows * 64, kBlock, (1 << 14) - 3), kBlock, 0, stream>>>(
+        row_ptr, col, w, n_rows, out_ptr, replace_when_short, rows, out_col, out_w);
+    TFGX_LAUNCH_CHECK("sample_wave_per_row_kernel");
+    return TFGX_OK;
 }
 
 }  // namespace tfgx

@@ -13,6 +13,7 @@
 // Nothing is passed between waves; the two phases of a tile are ordered by a wave-level fence (LDS executes one wave's
 // instructions in order).
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "tfgx_sample_rows.h"
 #include "../../include/tfgx_samplereduce.h"
 #include "../../include/tfgx_nbrstatic.h"
@@ -23,7 +24,6 @@ namespace {
 #define TFGX_STR_(v) #v
 #define TFGX_STR(v) TFGX_STR_(v)
 
-constexpr int64_t kMaxSize = (int64_t(1) << 31) - 1;
 constexpr int kSlots = 4 * TFGX_SAMPLEREDUCE_MAX_DRAWS;      // (id, weight) pairs a wave keeps: 8 KiB
 constexpr int kWaves = kBlock / kWave;
 constexpr int kInFlight = 4;                                 // row loads in flight per lane
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void samplereduce_kernel(const int32_t* __r
                 ok = 1;
                 s = row_ptr[r];
                 d = row_ptr[r + 1] - s;
-                m = d <= 0 ? 0 : (replace_when_short ? k : min(d, k));
+                m = sample_row_draws(d, k, replace_when_short);
                 if (out_count != nullptr) out_count[base + lane] = m;
             }
         }
@@ -173,31 +173,6 @@ __global__ __launch_bounds__(kBlock) void samplereduce_kernel(const int32_t* __r
         }
         wave_sync();           // the next tile's draws overwrite these slots
     }
-}
-
-int check_size(const char* fn, const char* name, int64_t v)
-{
-    if (v < 0) {
-        set_error("%s: negative size (%s = %lld)", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (v >= kMaxSize) {
-        set_error("%s: %s = %lld does not fit int32", fn, name, (long long)v);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    return TFGX_OK;
-}
-
-int null_arg(const char* fn, const char* name)
-{
-    set_error("%s: %s is null", fn, name);
-    return TFGX_ERR_INVALID_ARG;
-}
-
-int bad_arg(const char* fn, const char* what, long long v)
-{
-    set_error("%s: %s (got %lld)", fn, what, v);
-    return TFGX_ERR_INVALID_ARG;
 }
 
 }  // namespace

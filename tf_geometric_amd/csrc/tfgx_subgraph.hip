@@ -12,6 +12,7 @@
 // Gather-scale rows (x[idx] * s[idx]) and its backward (one row per wave over ALL parent rows through node_map: no
 // memset, no atomics, fixed-order reduction).  Integer atomics only (flags, duplicate detection); never on floats.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include <hipcub/hipcub.hpp>
 
 namespace tfgx {
@@ -20,8 +21,6 @@ namespace {
 constexpr int kTileItems = 8;                          // edges per thread per tile
 constexpr int kTile = kBlock * kTileItems;             // 2048 edges per workgroup
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 inline int64_t num_tiles(int64_t E) { return (E + kTile - 1) / kTile; }
 
@@ -295,12 +294,12 @@ Layout layout(int64_t n, int64_t E, int64_t m, int with_plan)
     int32_t* out = nullptr;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tiles, in, out, static_cast<int>(L.nt + 1));
     if (with_plan) (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_rows, in, out, static_cast<int>(m + 1));
-    L.temp_bytes = align_up(scan_tiles > scan_rows ? scan_tiles : scan_rows);
+    L.temp_bytes = align256(scan_tiles > scan_rows ? scan_tiles : scan_rows);
     L.off_tile_cnt = 0;
-    L.off_tile_off = align_up(sizeof(int32_t) * size_t(L.nt + 1));
-    L.off_row_cnt = L.off_tile_off + align_up(sizeof(int32_t) * size_t(L.nt + 3));
-    L.off_rank = L.off_row_cnt + (with_plan ? align_up(sizeof(int32_t) * size_t(m + 1)) : 0);
-    L.off_temp = L.off_rank + (with_plan ? align_up(sizeof(int32_t) * size_t(E > 0 ? E : 1)) : 0);
+    L.off_tile_off = align256(sizeof(int32_t) * size_t(L.nt + 1));
+    L.off_row_cnt = L.off_tile_off + align256(sizeof(int32_t) * size_t(L.nt + 3));
+    L.off_rank = L.off_row_cnt + (with_plan ? align256(sizeof(int32_t) * size_t(m + 1)) : 0);
+    L.off_temp = L.off_rank + (with_plan ? align256(sizeof(int32_t) * size_t(E > 0 ? E : 1)) : 0);
     L.total = L.off_temp + L.temp_bytes;
     return L;
 }

@@ -8,12 +8,11 @@
 // order is the reference's: sources ascending, scores descending, equal scores in the caller's order (tf.argsort
 // DESCENDING is top_k underneath: the lower index wins a tie; the sort by source id is the same top_k on negated ids).
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include <hipcub/hipcub.hpp>
 
 namespace tfgx {
 namespace {
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 inline int id_bits(int64_t n)
 {
@@ -108,15 +107,15 @@ TopkLayout topk_layout(int64_t n, int64_t num_segments)
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t2, v, vo, static_cast<int>(ns));
     TopkLayout L;
     size_t o = 0;
-    L.keys = o, o += align_up(8 * nn);
-    L.keys_s = o, o += align_up(8 * nn);
-    L.vals = o, o += align_up(4 * nn);
-    L.vals_s = o, o += align_up(4 * nn);
-    L.start = o, o += align_up(4 * ns);
-    L.node_k = o, o += align_up(4 * ns);
-    L.offset = o, o += align_up(4 * ns);
+    L.keys = o, o += align256(8 * nn);
+    L.keys_s = o, o += align256(8 * nn);
+    L.vals = o, o += align256(4 * nn);
+    L.vals_s = o, o += align256(4 * nn);
+    L.start = o, o += align256(4 * ns);
+    L.node_k = o, o += align256(4 * ns);
+    L.offset = o, o += align256(4 * ns);
     L.bad = o, o += 256;
-    L.temp = o, o += align_up(t1 > t2 ? t1 : t2) + 256;
+    L.temp = o, o += align256(t1 > t2 ? t1 : t2) + 256;
     L.total = o;
     return L;
 }

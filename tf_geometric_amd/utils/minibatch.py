@@ -106,8 +106,7 @@ def _check_ids(ids, what):
         raise ValueError("{} must be one-dimensional, got shape {}".format(what, shape))
 
 
-def check_sample_blocks_args(seeds, fanouts):
-    """The refusals of sample_blocks that need no device."""
+def _check_fanouts(fanouts):
     if not isinstance(fanouts, (list, tuple)) or len(fanouts) == 0:
         raise ValueError("fanouts must be a non-empty list of neighbour counts, one per layer (input side first)")
     for f in fanouts:
@@ -115,12 +114,32 @@ def check_sample_blocks_args(seeds, fanouts):
             raise ValueError("fanouts must be integers, got {!r}".format(f))
         if f < 0:
             raise ValueError("fanouts must not be negative, got {}".format(f))
+
+
+def check_sample_blocks_args(seeds, fanouts):
+    """The refusals of sample_blocks that need no device."""
+    _check_fanouts(fanouts)
     _check_ids(seeds, "seeds")
+
+
+def _fresh_seed():
+    """seed=None: one from torch's host generator (reproducible under torch.manual_seed, different on every call)."""
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+def _table(x, n_nodes, who):
+    """The refusals of a float32 feature table, in the caller's name: (the table with dense rows, its leading dimension, F)."""
+    if x.dim() != 2 or int(x.shape[1]) < 1:
+        raise ValueError("{}: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(who, tuple(x.shape)))
+    if int(x.shape[0]) < n_nodes:
+        raise ValueError("{}: x has {} rows but the sampler's graph has {} nodes".format(who, int(x.shape[0]), n_nodes))
+    x2, ldx = L.row_major_2d(x)
+    return x2, ldx, int(x.shape[1])
 
 
 class _State(object):
     """What a sampler keeps for the row-list calls: row_ptr padded to every node id (nodes that only appear as neighbours have
-    degree 0) and the relabel table, both made once."""
+    degree 0) and the relabel table, both made once.  begin() / end() bracket a call that writes to the table."""
 
     def __init__(self, sampler):
         plan = sampler.plan
@@ -131,6 +150,16 @@ class _State(object):
         self.table = torch.full((self.n_nodes,), L.NBRBLOCK_EMPTY, dtype=torch.int32, device=dev)
         self.dirty = False
 
+    def begin(self):
+        if self.dirty:           # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
+            self.table.fill_(L.NBRBLOCK_EMPTY)
+        self.dirty = True        # until end() has reset what the call wrote
+
+    def end(self, lib, node_list, n, stream):
+        """Empties the entries of the n ids the call wrote."""
+        L.check(lib.tfgx_nbrblock_reset(L.ptr(self.table), self.n_nodes, L.ptr(node_list), n, stream), "tfgx_nbrblock_reset")
+        self.dirty = False
+
 
 def _state(sampler):
     st = getattr(sampler, "_nbrblock", None)
@@ -139,10 +168,14 @@ def _state(sampler):
     return st
 
 
+def _flat_ids(ids, dev):
+    t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids)))
+    return t.detach().to(dev).reshape(-1)
+
+
 def _ids_on_device(ids, n_nodes, dev):
     """(int32 ids, a device flag that is non-zero when an id wider than int32 was out of range before the cast)."""
-    t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(ids)))
-    t = t.detach().to(dev).reshape(-1)
+    t = _flat_ids(ids, dev)
     if t.dtype == torch.int32:
         return t.contiguous(), None
     wide_bad = ((t < 0) | (t >= n_nodes)).any().to(torch.int32) if t.numel() else None
@@ -228,7 +261,7 @@ def sample_rows(sampler, rows, k=None, ratio=None, padding=False, seed=None):
     L.require_gpu()
     refuse_capture("RandomNeighborSampler.sample_rows")
     if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = _fresh_seed()
     ei, ew, _ = _sample_rows_device(sampler, rows, k, ratio, padding, seed, "sample_rows")
     return (ei.cpu().numpy(), ew.cpu().numpy()) if sampler._numpy else (ei, ew)
 
@@ -281,13 +314,10 @@ def sample_reduce(sampler, rows, x, k, op="mean", padding=False, seed=None, rati
     route = sample_reduce_route(k, x)
     x = L.as_f32(x)
     st = _state(sampler)
-    if x.dim() != 2 or int(x.shape[1]) < 1:
-        raise ValueError("sample_reduce: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
-    if int(x.shape[0]) < st.n_nodes:
-        raise ValueError("sample_reduce: x has {} rows but the sampler's graph has {} nodes".format(int(x.shape[0]), st.n_nodes))
+    x2, ldx, F = _table(x, st.n_nodes, "sample_reduce")
     if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-    dev, F = st.table.device, int(x.shape[1])
+        seed = _fresh_seed()
+    dev = st.table.device
     if route == "composed":
         ei, ew, out_ptr = _sample_rows_device(sampler, rows, int(k), None, padding, seed, "sample_reduce")
         n_rows = int(out_ptr.shape[0]) - 1
@@ -315,7 +345,6 @@ def sample_reduce(sampler, rows, x, k, op="mean", padding=False, seed=None, rati
     count = torch.zeros(n_rows, dtype=torch.int32, device=dev) if return_count else None
     if n_rows == 0:
         return (out, count) if return_count else out
-    x2, ldx = L.row_major_2d(x)
     ldo = int(out.stride(0)) if n_rows > 1 else F
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     if wide_bad is not None:
@@ -336,16 +365,14 @@ def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None, fuse_input_
     lib = L.require_gpu()
     refuse_capture("RandomNeighborSampler.sample_blocks")
     if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = _fresh_seed()
     hop_seeds = [hop_seed(seed, h) for h in range(len(fanouts))]
     # fuse_input_hop: the outermost hop (fanouts[0], the last seed) is left to sample_reduce; the hops before it run as ever
     n_hops = len(fanouts) - (1 if fuse_input_hop else 0)
     input_hop = (int(fanouts[0]), bool(padding), hop_seeds[-1]) if fuse_input_hop else None
     st = _state(sampler)
     dev = st.table.device
-    if st.dirty:             # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
-        st.table.fill_(L.NBRBLOCK_EMPTY)
-    st.dirty = True          # until this call has reset what it wrote
+    st.begin()
     stream = L.stream_ptr()
     syncs = 0
 
@@ -401,8 +428,7 @@ def sample_blocks(sampler, seeds, fanouts, padding=False, seed=None, fuse_input_
         if h + 1 < n_hops:
             cnt, out_ptr, total = next_cnt[:n_src].contiguous(), next_ptr[:n_src + 1].contiguous(), next_total
 
-    L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node_list), n_known, stream), "tfgx_nbrblock_reset")
-    st.dirty = False
+    st.end(lib, node_list, n_known, stream)
     return SampledMinibatch(blocks[::-1], node_list[:n_known].contiguous(), num_seeds, hop_seeds, syncs, input_hop, sampler)
 
 
@@ -436,13 +462,7 @@ def check_static_args(fanouts, ratio=None):
     if isinstance(fanouts, (list, tuple)) and any(f is None for f in fanouts):
         raise ValueError("sample_blocks_static has no form for a fan-out of None (k=None keeps every neighbour: a row may be as "
                          "long as the graph, so there is no capacity): pass integer fan-outs, or use sample_blocks")
-    if not isinstance(fanouts, (list, tuple)) or len(fanouts) == 0:
-        raise ValueError("fanouts must be a non-empty list of neighbour counts, one per layer (input side first)")
-    for f in fanouts:
-        if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
-            raise ValueError("fanouts must be integers, got {!r}".format(f))
-        if f < 0:
-            raise ValueError("fanouts must not be negative, got {}".format(f))
+    _check_fanouts(fanouts)
 
 
 def static_capacities(B, fanouts):
@@ -467,7 +487,7 @@ def _device_seed(seed, dev, who):
             raise RuntimeError("{}: seed=None inside a hipGraph capture would freeze one by-value seed into the graph and every "
                                "replay would draw the same sample: pass an int64 one-element device tensor and advance it inside "
                                "the captured function (state.add_(1))".format(who))
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = _fresh_seed()
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("{}: seed must be an int, an int64 one-element device tensor or None, got {!r}".format(who, seed))
     s = int(seed) & ((1 << 64) - 1)
@@ -531,13 +551,8 @@ class StaticMinibatch(object):
                 return torch.where(self.live[:, None], rows, torch.zeros((), dtype=x.dtype, device=x.device))
         lib = L.require_gpu()
         x = L.as_f32(x)
-        if x.dim() != 2 or int(x.shape[1]) < 1:
-            raise ValueError("StaticMinibatch.gather: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
-        if int(x.shape[0]) < max(self._n_nodes, 1):
-            raise ValueError("StaticMinibatch.gather: x has {} rows but the sampler's graph has {} nodes".format(
-                int(x.shape[0]), self._n_nodes))
-        x2, ldx = L.row_major_2d(x)
-        M, F = int(self.node_index.shape[0]), int(x2.shape[1])
+        x2, ldx, F = _table(x, self._n_nodes, "StaticMinibatch.gather")
+        M = int(self.node_index.shape[0])
         out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
         L.check(lib.tfgx_nbrstatic_gather_rows_f32(L.ptr(x2), ldx, L.ptr(self.node_index), M, F, L.ptr(out), F, L.stream_ptr()),
                 "tfgx_nbrstatic_gather_rows_f32")
@@ -559,12 +574,8 @@ class StaticMinibatch(object):
         k, padding, hop = self.input_hop
         st = _state(self._sampler)
         x = L.as_f32(x)
-        if x.dim() != 2 or int(x.shape[1]) < 1:
-            raise ValueError("input_aggregate: x must be a [num_nodes, F] table with F >= 1, got shape {}".format(tuple(x.shape)))
-        if int(x.shape[0]) < st.n_nodes:
-            raise ValueError("input_aggregate: x has {} rows but the sampler's graph has {} nodes".format(int(x.shape[0]), st.n_nodes))
-        x2, ldx = L.row_major_2d(x)
-        M, F = int(self.node_index.shape[0]), int(x2.shape[1])
+        x2, ldx, F = _table(x, st.n_nodes, "input_aggregate")
+        M = int(self.node_index.shape[0])
         out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
         L.check(lib.tfgx_nbrstatic_input_hop_f32(
             L.ptr(st.row_ptr), L.ptr(self._sampler.plan.col), L.ptr(self._sampler.w_csr), st.n_nodes, L.ptr(self.node_index), M,
@@ -576,8 +587,7 @@ class StaticMinibatch(object):
 def _static_seeds_on_device(seeds, n_nodes, dev):
     """int32 seeds on the device without a read: an id wider than int32 is clamped to an out-of-range int32 first (the kernel
     then flags it as it flags any other)."""
-    t = seeds if isinstance(seeds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds)))
-    t = t.detach().to(dev).reshape(-1)
+    t = _flat_ids(seeds, dev)
     if t.dtype != torch.int32:
         t = t.long().clamp(min=-2, max=n_nodes).to(torch.int32)
     return t.contiguous()
@@ -607,9 +617,7 @@ def sample_blocks_static(sampler, seeds, fanouts, padding=False, seed=None, fuse
     ks = [int(k) for k in (fanouts[1:] if fuse_input_hop else fanouts)][::-1]
     cap = _capacities(B, ks)
     input_hop = (k_input, bool(padding), n_layers - 1) if fuse_input_hop else None
-    if st.dirty:             # a call that raised midway left entries behind: refill once (the only O(n_nodes) step)
-        st.table.fill_(L.NBRBLOCK_EMPTY)
-    st.dirty = True
+    st.begin()
     stream = L.stream_ptr()
     n_total = cap.rows[-1]
     node = torch.empty(n_total, dtype=torch.int32, device=dev)
@@ -653,6 +661,5 @@ def sample_blocks_static(sampler, seeds, fanouts, padding=False, seed=None, fuse
             plan.hub_threshold, plan._hub, plan._row_order = thr, False, False
         attach_plan(ei, plan)
         blocks.append(SampledBlock(ei, ew, R, Rn))
-    L.check(lib.tfgx_nbrblock_reset(L.ptr(st.table), st.n_nodes, L.ptr(node), n_total, stream), "tfgx_nbrblock_reset")
-    st.dirty = False
+    st.end(lib, node, n_total, stream)
     return StaticMinibatch(blocks[::-1], node, B, counts, flag, seed_t, cap, st.n_nodes, input_hop, sampler)
