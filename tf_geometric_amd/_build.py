@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
-           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip"]
+           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip", "tfgx_collate_static.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -33,6 +33,7 @@ def build(force=False, verbose=True):
     fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
     gemm_hdrs = [os.path.join(CSRC, "tfgx_gemm_kernels.h"), os.path.join(CSRC, "tfgx_mfma.h")]      # the GEMM templates both GEMM sources instantiate
     sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's bodies and kernel pair: every sampler is compiled from it
+    collate_hdr = os.path.join(CSRC, "tfgx_collate_tiles.h")   # the per-element bodies both collate kernels are compiled from
     host_hdr = os.path.join(CSRC, "tfgx_host.h")               # the refusals and workspace layouts of the entry points
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
                 "tfgx_misc.hip": [sample_hdr],
@@ -55,7 +56,9 @@ def build(force=False, verbose=True):
                 "tfgx_asap.hip": [host_hdr, os.path.join(_HERE, "..", "include", "tfgx_asap.h")],
                 "tfgx_seggram.hip": [os.path.join(_HERE, "..", "include", "tfgx_seggram.h")],
                 "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")],
-                "tfgx_collate.hip": [os.path.join(_HERE, "..", "include", "tfgx_collate.h")]}
+                "tfgx_collate.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h")],
+                "tfgx_collate_static.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
+                                            os.path.join(_HERE, "..", "include", "tfgx_collate_static.h")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

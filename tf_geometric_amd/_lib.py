@@ -392,6 +392,22 @@ class CollateArgs(ctypes.Structure):
     ]
 
 
+class CollateStaticArgs(ctypes.Structure):
+    """struct tfgx_static_batch_args (include/tfgx_collate_static.h)."""
+    _fields_ = [
+        ("ds_x", ctypes.c_void_p), ("ds_ldx", ctypes.c_int64), ("F", ctypes.c_int64),
+        ("ds_row", ctypes.c_void_p), ("ds_col", ctypes.c_void_p), ("ds_w", ctypes.c_void_p),
+        ("ds_n", ctypes.c_int64), ("ds_e", ctypes.c_int64),
+        ("table", ctypes.c_void_p), ("B", ctypes.c_int64),
+        ("n_cap", ctypes.c_int64), ("e_cap", ctypes.c_int64), ("sinks", ctypes.c_int64), ("sink_degree", ctypes.c_int64),
+        ("out_x", ctypes.c_void_p), ("out_ldx", ctypes.c_int64), ("out_node_graph_index", ctypes.c_void_p),
+        ("out_row", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_edge_graph_index", ctypes.c_void_p),
+        ("out_w", ctypes.c_void_p),
+        ("plan", ctypes.POINTER(CollatePlan)), ("plan_t", ctypes.POINTER(CollatePlan)),
+        ("graph_row_ptr", ctypes.c_void_p),
+    ]
+
+
 # include/tfgx_collate.h (minibatch assembly out of a packed device dataset, with sort-free plans)
 COLLATE_ABI_VERSION = 1
 COLLATE_TILE = 1024          # TFGX_COLLATE_TILE: output elements per workgroup
@@ -442,6 +458,17 @@ NBRSTATIC_SIGNATURES = {
                                                     _P, _P, _P]),
 }
 
+# include/tfgx_collate_static.h (fixed-shape batches: device-resident ids, capacities the host knows, no reads)
+COLLATE_STATIC_ABI_VERSION = 1
+COLLATE_STATIC_DEAD = -1             # TFGX_STATIC_BATCH_DEAD: a dead slot of the id list
+COLLATE_STATIC_BAD_ID, COLLATE_STATIC_OVERFLOW = 1, 2      # bits of counts[3]
+COLLATE_STATIC_MAX_SLOTS = 1 << 20   # TFGX_STATIC_BATCH_MAX_SLOTS
+COLLATE_STATIC_SIGNATURES = {
+    "tfgx_static_batch_version": (ctypes.c_int, []),
+    "tfgx_static_batch_table": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "tfgx_static_batch": (ctypes.c_int, [ctypes.POINTER(CollateStaticArgs), _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry ("Adding a header").
@@ -462,13 +489,14 @@ ABIS = (
     Abi("tfgx_nbrblock.h", "tfgx_nbrblock_version", NBRBLOCK_ABI_VERSION, NBRBLOCK_SIGNATURES, ()),
     Abi("tfgx_samplereduce.h", "tfgx_samplereduce_version", SAMPLEREDUCE_ABI_VERSION, SAMPLEREDUCE_SIGNATURES, ()),
     Abi("tfgx_nbrstatic.h", "tfgx_nbrstatic_version", NBRSTATIC_ABI_VERSION, NBRSTATIC_SIGNATURES, ()),
+    Abi("tfgx_collate_static.h", "tfgx_static_batch_version", COLLATE_STATIC_ABI_VERSION, COLLATE_STATIC_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module
 STRUCTS = {
     "tfgx_reduce_args": ReduceArgs, "tfgx_gat_args": GatArgs, "tfgx_hub_lists": HubLists,
     "tfgx_gat_backward_args": GatBackwardArgs, "tfgx_drop_edge_plan": DropEdgePlan, "tfgx_collate_plan": CollatePlan,
-    "tfgx_collate_args": CollateArgs,
+    "tfgx_collate_args": CollateArgs, "tfgx_static_batch_args": CollateStaticArgs,
 }
 
 

@@ -380,3 +380,59 @@ class BatchGraph(Graph):
             "'BatchGraph.convert_edge_to_directed(self, merge_mode)' is deprecated, use 'BatchGraph.to_directed(inplace=True)' instead",
             DeprecationWarning)
         return self.to_directed(merge_mode, inplace=True)
+
+
+class StaticBatchGraph(BatchGraph):
+    """What ``GraphStore.collate_static`` returns: a batch of ``B`` slots at sizes the host knows (``capacities``), with inert
+    padding.  ``num_graphs == B + 1``: slot ``B`` is the dead graph that owns every padded row.  ``graph_mask`` bool [B] says
+    which slots are live; ``counts`` int32 [4] on the device holds live graphs, live nodes, live edges and the flags
+    ``check()`` reads.  ``y`` has one row per slot; a dead slot holds graph 0's label, so mask it:
+
+        h = gcn1([b.x, b.edge_index, b.edge_weight], cache=b.cache, training=True)
+        logits = dense(b.readout(h, "mean"))
+        per_slot = cross_entropy(logits, b.y.reshape(-1), reduction="none")
+        loss = torch.where(b.graph_mask, per_slot, 0.0).sum() / b.counts[0].clamp(min=1)
+
+    Nothing here reads the device back except ``check()``."""
+
+    _READOUTS = ("mean", "sum", "max", "min")
+
+    def __init__(self, x, edge_index, node_graph_index, edge_graph_index, y, edge_weight, ids, graph_mask, counts, capacities,
+                 store_len, given_ids=None):
+        super().__init__(x, edge_index, node_graph_index, edge_graph_index, y=y, edge_weight=edge_weight)
+        self.ids = ids                  # int32 [B], as the kernel read them (an id beyond int32 held to an out-of-range one)
+        self._given_ids = ids if given_ids is None else given_ids
+        self.graph_mask = graph_mask
+        self.counts = counts
+        self.capacities = capacities
+        self.num_slots = int(graph_mask.shape[0])
+        self._num_graphs = self.num_slots + 1
+        self._store_len = int(store_len)
+
+    def readout(self, h, op="mean"):
+        """[B, F]: the `op` ("mean" / "sum" / "max" / "min") of h over the nodes of each slot, through the graph plan the batch
+        carries (no sort, no host read).  The dead graph B is dropped, and the rows of dead slots are EXACTLY zero (torch.where
+        on graph_mask): an empty graph's max is float32 lowest, which overflows in the next dense layer, and inf * 0 in a weight
+        gradient is NaN."""
+        from ..nn.pool import common_pool as P
+        if op not in self._READOUTS:
+            raise ValueError("readout: op must be one of {}, got {!r}".format(self._READOUTS, op))
+        pooled = getattr(P, op + "_pool")(h, self.node_graph_index, self.num_graphs, cache=self.cache)[:self.num_slots]
+        return torch.where(self.graph_mask[:, None], pooled, torch.zeros((), dtype=pooled.dtype, device=pooled.device))
+
+    def check(self):
+        """The ONE host read of a static batch, when the caller wants it: ValueError naming the first id outside [-1, G), or
+        the first slot dropped because the batch would exceed max_nodes / max_edges.  Either slot is dead in this batch."""
+        B = self.num_slots
+        host = torch.cat([self.counts[3:4].long(), self._given_ids.reshape(-1).long(), self.graph_mask.long()]).cpu().numpy()      # the one read
+        flags, ids, mask = int(host[0]), host[1:1 + B], host[1 + B:] != 0
+        if flags == 0:
+            return self
+        if flags & L.COLLATE_STATIC_BAD_ID:
+            bad = np.nonzero((ids < -1) | (ids >= self._store_len))[0]
+            raise ValueError("collate_static: graph id {} (slot {} of the batch) is outside [0, {}) and is not -1".format(
+                int(ids[bad[0]]), int(bad[0]), self._store_len))
+        dropped = np.nonzero((ids >= 0) & (ids < self._store_len) & ~mask)[0]
+        raise ValueError("collate_static: slot {} (graph {}) and every later slot were dropped: the batch would exceed max_nodes "
+                         "= {} or max_edges = {}".format(int(dropped[0]), int(ids[dropped[0]]), self.capacities.max_nodes,
+                                                         self.capacities.max_edges))

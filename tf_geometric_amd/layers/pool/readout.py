@@ -2,7 +2,8 @@
 """Graph-level readouts as layer objects — the working form of tf_geometric.layers.{MeanPool, SumPool, MaxPool, MinPool}
 (layers/pool/common_pool.py: there the four subclasses derive from tf.keras.Model and hand the pooling function to
 keras' constructor, so they cannot be instantiated; the intended behaviour is CommonPool's, :6-19).
-inputs = [x, node_graph_index] or [x, node_graph_index, num_graphs]; one segment-reduce launch each."""
+inputs = [x, node_graph_index] or [x, node_graph_index, num_graphs]; one segment-reduce launch each.  cache= (the batch's cache
+dict) takes the graph plan the batch carries instead of sorting node_graph_index."""
 from ...nn.pool.common_pool import mean_pool, sum_pool, max_pool, min_pool
 from .._base import Layer
 
@@ -15,10 +16,12 @@ class CommonPool(Layer):
     def build(self, input_shapes):
         """Readouts own no weights."""
 
-    def call(self, inputs, training=None, mask=None):
+    def call(self, inputs, training=None, mask=None, cache=None):
         x, node_graph_index = inputs[0], inputs[1]
         num_graphs = inputs[2] if len(inputs) > 2 else None
-        return self.pool_func(x, node_graph_index, num_graphs)
+        if cache is None:
+            return self.pool_func(x, node_graph_index, num_graphs)
+        return self.pool_func(x, node_graph_index, num_graphs, cache=cache)
 
 
 def _readout(name, func):
