@@ -7,10 +7,16 @@ readouts summed, then Dense(128, relu) -> Dropout(0.5) -> Dense(64, relu) -> Den
 10-50 nodes with 37 one-hot node labels; a graph is of class 1 when it holds a planted motif — a 6-cycle of nodes with
 label 5 — and of class 0 when its label-5 nodes are scattered (same label counts, no cycle).
 
-    python examples/demo_sag_pool_h.py [--epochs 30] [--graphs 4000]
+    python examples/demo_sag_pool_h.py [--epochs 30] [--graphs 4000] [--static] [--capture]
 
 Every coarsening step runs on the induced-subgraph kernels; each pooled edge list carries a CSR plan derived from its
 parent's, so the GCNs of the next level do not sort.
+
+--static trains on fixed-shape batches instead: a GraphStore holds the training graphs on the device, a StaticLoader hands on
+graph ids from a device cursor, collate_static assembles them at capacities the host computed once, and every level is
+SAGPool.pool_static (a static batch in, a static batch out) with the readouts the batches carry — no host read anywhere in the
+step.  --capture (implies --static) records ids -> batch -> three levels -> loss -> backward -> Adam once with
+tfg.CapturedTrainStep and replays it.  Without either flag the program is what it was.
 """
 import argparse
 import math
@@ -136,6 +142,89 @@ class SAGPoolHModel(object):
         return AG.linear(h, k2, b2)
 
 
+def static_logits(model, batch, training=False, levels=None):
+    """The model on a StaticBatchGraph: one row of logits per SLOT (dead slots: the biases alone).  Level by level the pooled
+    batch replaces its parent (and is appended to `levels` when a list is given); mean || max readouts through the graph plan
+    each batch carries."""
+    h, outputs = batch.x, []
+    for gcn, sag_pool in zip(model.gcns, model.sag_pools):
+        h = gcn([h, batch.edge_index, batch.edge_weight], cache=batch.cache, training=training)
+        batch = sag_pool.pool_static(h, batch, training=training)
+        h = batch.x
+        if levels is not None:
+            levels.append(batch)
+        outputs.append(torch.cat([batch.readout(h, "mean"), batch.readout(h, "max")], dim=-1))
+    h = outputs[0] + outputs[1] + outputs[2]
+    (k0, b0), (k1, b1), (k2, b2) = model.mlp
+    h = AG.linear(h, k0, b0, tfg._lib.ACT_RELU)
+    if training:
+        h = torch.nn.functional.dropout(h, 0.5, training=True)
+    h = AG.linear(h, k1, b1, tfg._lib.ACT_RELU)
+    return AG.linear(h, k2, b2)
+
+
+def static_loss(model, batch, training=True):
+    """Mean cross-entropy over the LIVE slots (a dead slot holds graph 0's label: torch.where on graph_mask)."""
+    per_slot = torch.nn.functional.cross_entropy(static_logits(model, batch, training=training), batch.y.reshape(-1),
+                                                 reduction="none")
+    zero = torch.zeros((), dtype=per_slot.dtype, device=per_slot.device)
+    return torch.where(batch.graph_mask, per_slot, zero).sum() / batch.counts[0].clamp(min=1).to(per_slot.dtype)
+
+
+def graph_store(data, indices):
+    graphs = []
+    for i in indices:
+        node_labels, ei = data.graphs[i]
+        x = np.zeros((node_labels.size, NUM_LABELS), dtype=np.float32)
+        x[np.arange(node_labels.size), node_labels] = 1.0
+        graphs.append(tfg.Graph(x, ei, y=data.labels[i:i + 1]))
+    return tfg.data.GraphStore(graphs)
+
+
+def make_static_step(model, store, loader, capacities, opt, capture):
+    """step() -> the loss (a device scalar) of one training step on the loader's next batch.  capture=True records the step once
+    with tfg.CapturedTrainStep (opt must be capturable) and replays it."""
+    def loss_fn():
+        return static_loss(model, store.collate_static(loader.next_ids(), capacities))
+
+    if not capture:
+        def step():
+            opt.zero_grad(set_to_none=True)
+            loss = loss_fn()
+            loss.backward()
+            opt.step()
+            return loss
+        return step
+    cursor, rng_state = loader.cursor.clone(), torch.cuda.get_rng_state()
+    step = tfg.CapturedTrainStep(loss_fn, opt)
+    # the warm-up steps and the capture advanced the loader's cursor and the dropout generator; the constructor rolled the
+    # weights and the optimizer state back, these two are rolled back here: replay k then draws the batch AND the dropout
+    # masks of eager step k, so a --capture run trains exactly as a --static run does
+    loader.cursor.copy_(cursor)
+    torch.cuda.set_rng_state(rng_state)
+    return step
+
+
+def train_static(model, data, train_idx, test_batches, args):
+    """The --static / --capture route: the epochs of main() over fixed-shape batches."""
+    store = graph_store(data, train_idx)
+    loader = store.static_loader(args.batch_size, shuffle=True, seed=args.seed + 1)
+    cap = store.static_capacities(args.batch_size)
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr, capturable=args.capture)
+    step = make_static_step(model, store, loader, cap, opt, args.capture)
+    print("batches: collate_static{}; capacities: {} rows and {} edges for {} slots".format(
+        ", replayed" if args.capture else "", cap.n_cap, cap.e_cap, cap.batch_size), flush=True)
+    for epoch in range(args.epochs):
+        if epoch:
+            loader.reshuffle(args.seed + 1 + epoch)           # in place: the replay reads the new order
+        t0 = time.perf_counter()
+        losses = torch.stack([step().detach().clone() for _ in range(loader.steps_per_epoch)])
+        loss = float(losses.mean().item())                    # the one read of the epoch
+        ms = (time.perf_counter() - t0) * 1e3 / loader.steps_per_epoch
+        print("epoch {:3d}  loss {:.6f}  test accuracy {:.4f}  ({:.2f} ms / step)".format(
+            epoch, loss, evaluate(model, test_batches), ms), flush=True)
+
+
 def train_step(model, opt, batch):
     x, ei, gid, y, num_graphs = batch
     logits = model([x, ei, gid, num_graphs], training=True)
@@ -163,6 +252,8 @@ def main():
     p.add_argument("--batch-size", type=int, default=512)
     p.add_argument("--lr", type=float, default=5e-4)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--static", action="store_true", help="fixed-shape batches: collate_static and SAGPool.pool_static")
+    p.add_argument("--capture", action="store_true", help="replay the whole step from one hipGraph (implies --static)")
     args = p.parse_args()
     torch.manual_seed(args.seed)
     data = make_dataset(args.graphs, args.seed)
@@ -170,6 +261,8 @@ def main():
     train_idx = np.arange(n_test, len(data.graphs))
     test_batches = [make_batch(data, list(range(i, min(i + args.batch_size, n_test)))) for i in range(0, n_test, args.batch_size)]
     model = SAGPoolHModel(data.num_features, data.num_classes, seed=args.seed)
+    if args.static or args.capture:
+        return train_static(model, data, train_idx, test_batches, args)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     rng = np.random.Generator(np.random.PCG64(args.seed + 1))
     train_batches = None

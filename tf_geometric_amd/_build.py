@@ -14,7 +14,8 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip", "tfgx_gemm.hip", "tfgx_gemm_h16.hip", "tfgx_misc.hip", "tfgx_backward.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
-           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip", "tfgx_collate_static.hip"]
+           "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip", "tfgx_collate_static.hip",
+           "tfgx_pool_static.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -35,10 +36,11 @@ def build(force=False, verbose=True):
     sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's bodies and kernel pair: every sampler is compiled from it
     collate_hdr = os.path.join(CSRC, "tfgx_collate_tiles.h")   # the per-element bodies both collate kernels are compiled from
     host_hdr = os.path.join(CSRC, "tfgx_host.h")               # the refusals and workspace layouts of the entry points
+    topk_hdr = os.path.join(CSRC, "tfgx_topk_keys.h")          # the score key and the node_k rule both selections share
     own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
                 "tfgx_misc.hip": [sample_hdr],
                 "tfgx_plan.hip": [host_hdr], "tfgx_plan_ext.hip": [host_hdr], "tfgx_subgraph.hip": [host_hdr],
-                "tfgx_topk.hip": [host_hdr], "tfgx_poolgrad.hip": [host_hdr],
+                "tfgx_topk.hip": [host_hdr, topk_hdr], "tfgx_poolgrad.hip": [host_hdr],
                 "tfgx_nbrblock.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
                 "tfgx_samplereduce.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
                                           os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
@@ -58,7 +60,9 @@ def build(force=False, verbose=True):
                 "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")],
                 "tfgx_collate.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h")],
                 "tfgx_collate_static.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
-                                            os.path.join(_HERE, "..", "include", "tfgx_collate_static.h")]}
+                                            os.path.join(_HERE, "..", "include", "tfgx_collate_static.h")],
+                "tfgx_pool_static.hip": [host_hdr, topk_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
+                                         os.path.join(_HERE, "..", "include", "tfgx_pool_static.h")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -469,6 +469,35 @@ COLLATE_STATIC_SIGNATURES = {
     "tfgx_static_batch": (ctypes.c_int, [ctypes.POINTER(CollateStaticArgs), _P]),
 }
 
+class StaticPoolArgs(ctypes.Structure):
+    """struct tfgx_static_pool_args (include/tfgx_pool_static.h)."""
+    _fields_ = [
+        ("row", ctypes.c_void_p), ("col", ctypes.c_void_p), ("w", ctypes.c_void_p), ("edge_graph_index", ctypes.c_void_p),
+        ("n_cap", ctypes.c_int64), ("e_cap", ctypes.c_int64), ("B", ctypes.c_int64), ("sinks", ctypes.c_int64),
+        ("sink_degree", ctypes.c_int64),
+        ("node_map", ctypes.c_void_p), ("node_index", ctypes.c_void_p), ("pooled_row_ptr", ctypes.c_void_p),
+        ("n_cap_out", ctypes.c_int64),
+        ("out_row", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_edge_id", ctypes.c_void_p),
+        ("out_edge_graph_index", ctypes.c_void_p), ("out_w", ctypes.c_void_p),
+        ("plan", ctypes.POINTER(CollatePlan)), ("plan_t", ctypes.POINTER(CollatePlan)),
+        ("counts", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+# include/tfgx_pool_static.h (one fixed-shape SAGPool level: static batch in, static batch out, no reads)
+STATIC_POOL_ABI_VERSION = 1
+STATIC_POOL_MAX_GRAPH_NODES = 4096   # TFGX_STATIC_POOL_MAX_GRAPH_NODES: the longest graph the selection ranks in LDS
+STATIC_POOL_CLAMPED, STATIC_POOL_TOO_LONG = 4, 8      # bits of counts[3], beside the two of collate_static
+STATIC_POOL_MAX_SLOTS = 1 << 20      # TFGX_STATIC_POOL_MAX_SLOTS
+STATIC_POOL_SIGNATURES = {
+    "tfgx_static_pool_version": (ctypes.c_int, []),
+    "tfgx_static_pool_table": (ctypes.c_int, [_P, _P, _I64, _I32, _F32, _I64, _I64, _P, _P, _P]),
+    "tfgx_static_pool_select": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "tfgx_static_pool_edges_workspace_bytes": (_SZ, [_I64, _I64]),
+    "tfgx_static_pool_edges": (ctypes.c_int, [ctypes.POINTER(StaticPoolArgs), _P]),
+    "tfgx_static_pool_gather_scale_rows_f32": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry (DESIGN.md, "Adding a header").
@@ -490,6 +519,7 @@ ABIS = (
     Abi("tfgx_samplereduce.h", "tfgx_samplereduce_version", SAMPLEREDUCE_ABI_VERSION, SAMPLEREDUCE_SIGNATURES, ()),
     Abi("tfgx_nbrstatic.h", "tfgx_nbrstatic_version", NBRSTATIC_ABI_VERSION, NBRSTATIC_SIGNATURES, ()),
     Abi("tfgx_collate_static.h", "tfgx_static_batch_version", COLLATE_STATIC_ABI_VERSION, COLLATE_STATIC_SIGNATURES, ()),
+    Abi("tfgx_pool_static.h", "tfgx_static_pool_version", STATIC_POOL_ABI_VERSION, STATIC_POOL_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module
@@ -497,6 +527,7 @@ STRUCTS = {
     "tfgx_reduce_args": ReduceArgs, "tfgx_gat_args": GatArgs, "tfgx_hub_lists": HubLists,
     "tfgx_gat_backward_args": GatBackwardArgs, "tfgx_drop_edge_plan": DropEdgePlan, "tfgx_collate_plan": CollatePlan,
     "tfgx_collate_args": CollateArgs, "tfgx_static_batch_args": CollateStaticArgs,
+    "tfgx_static_pool_args": StaticPoolArgs,
 }
 
 

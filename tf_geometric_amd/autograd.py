@@ -1159,6 +1159,40 @@ def gather_scale(x, idx, node_map, s=None):
     return _GatherScale.apply(x, s, L.as_i32(idx, x.device), node_map)
 
 
+class _GatherScaleStatic(torch.autograd.Function):
+    """_GatherScale at a fixed shape (nn.sag_pool_static): idx holds -1 for the dead pooled rows, which come out exactly 0
+    (tfgx_static_pool_gather_scale_rows_f32: a clamped load, then a select).  The backward is _GatherScale's."""
+
+    @staticmethod
+    def forward(ctx, x, s, idx, node_map):
+        lib = L.require_gpu()
+        x2, ldx = L.row_major_2d(x)
+        M, F = int(idx.shape[0]), int(x2.shape[1])
+        out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
+        L.check(lib.tfgx_static_pool_gather_scale_rows_f32(L.ptr(x2), ldx, int(x2.shape[0]), L.ptr(idx), L.ptr(s), M, F, L.ptr(out),
+                                                           max(F, 1), L.stream_ptr()), "tfgx_static_pool_gather_scale_rows_f32")
+        ctx.save_for_backward(x2, s, node_map)
+        ctx.has_s = s is not None
+        return out
+
+    backward = staticmethod(_GatherScale.backward)
+
+
+def gather_scale_static(x, idx, node_map, s=None):
+    """gather_scale for a pooled static batch: idx int32 [n_cap'] with -1 for dead rows (zero rows of the result), node_map
+    int32 [n_cap].  Differentiable wrt x and s."""
+    n = int(x.shape[0])
+    if s is not None:
+        s = L.as_f32(s, x.device)
+        if s.numel() != n:
+            raise ValueError("the node score must hold one value per node ([{0}] or [{0}, 1]), got shape {1}".format(
+                n, tuple(s.shape)))
+        s = s.reshape(-1)
+        if not s.is_contiguous():
+            s = s.contiguous()
+    return _GatherScaleStatic.apply(x, s, idx, node_map)
+
+
 def gather_edge_values(w, edge_id):
     """w[edge_id] for a 1-D float32 tensor (tfgx_permute_rows_f32 with width 1)."""
     lib = L.require_gpu()

@@ -9,6 +9,7 @@
 // DESCENDING is top_k underneath: the lower index wins a tie; the sort by source id is the same top_k on negated ids).
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_topk_keys.h"      // descending_bits, topk_node_k: shared with tfgx_pool_static.hip
 #include <hipcub/hipcub.hpp>
 
 namespace tfgx {
@@ -19,14 +20,6 @@ inline int id_bits(int64_t n)
     int b = 1;
     while (b < 31 && (int64_t(1) << b) < n) ++b;
     return b;
-}
-
-// ascending unsigned order of the result == DESCENDING float order; -0.0 and +0.0 compare equal (as in top_k)
-__device__ __forceinline__ uint32_t descending_bits(float f)
-{
-    uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;   // order-preserving map of IEEE-754 onto unsigned
-    return ~u;
 }
 
 __global__ void topk_make_keys(const int32_t* __restrict__ seg, const float* __restrict__ score, int64_t n,
@@ -58,8 +51,7 @@ __global__ void topk_segment_starts(const uint64_t* __restrict__ keys_s, int64_t
     }
 }
 
-// node_k (topk_pool.py:62-71): min(k, count), or ceil(float32(count) * float32(ratio)) — clamped to count, where the
-// reference would start selecting its padding columns for ratio > 1
+// node_k of every segment (topk_node_k, tfgx_topk_keys.h)
 __global__ void topk_counts(const int32_t* __restrict__ start, int32_t num_segments, int32_t k, float ratio,
                             int32_t* __restrict__ node_k)
 {
@@ -69,7 +61,7 @@ __global__ void topk_counts(const int32_t* __restrict__ start, int32_t num_segme
         int32_t v = 0;
         if (s < num_segments) {
             const int32_t cnt = start[s + 1] - start[s];
-            v = (k >= 0) ? min(k, cnt) : min(cnt, int32_t(ceilf(float(cnt) * ratio)));
+            v = topk_node_k(cnt, k, ratio);
         }
         node_k[s] = v;   // node_k[num_segments] = 0: the exclusive scan leaves the total there
     }

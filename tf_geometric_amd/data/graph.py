@@ -408,6 +408,10 @@ class StaticBatchGraph(BatchGraph):
         self.num_slots = int(graph_mask.shape[0])
         self._num_graphs = self.num_slots + 1
         self._store_len = int(store_len)
+        self._store = None              # the GraphStore behind the batch (collate_static sets it; a pooled batch hands it on)
+        self.graph_row_ptr = None       # int32 [B + 2]: the slots' row offsets, the live total, n_cap (the graph plan's row_ptr)
+        self.node_index = None          # a pooled batch (nn.sag_pool_static): pooled row -> parent row, -1 for a dead row
+        self.edge_id = None             # ... and pooled edge -> parent edge, -1 for a padded one
 
     def readout(self, h, op="mean"):
         """[B, F]: the `op` ("mean" / "sum" / "max" / "min") of h over the nodes of each slot, through the graph plan the batch
@@ -420,14 +424,60 @@ class StaticBatchGraph(BatchGraph):
         pooled = getattr(P, op + "_pool")(h, self.node_graph_index, self.num_graphs, cache=self.cache)[:self.num_slots]
         return torch.where(self.graph_mask[:, None], pooled, torch.zeros((), dtype=pooled.dtype, device=pooled.device))
 
+    def pooled_capacities(self, k=None, ratio=None):
+        """StaticBatchCapacities of this batch pooled by nn.sag_pool_static(k= / ratio=): host arithmetic, no device.  The
+        batch size, max_edges (kept edges are a subset of the live ones), the sink degree and the sinks P stay; max_nodes
+        becomes m_max, a bound of the kept nodes sum_g k_g under the kernel's rule k_g = min(k, n_g), or
+        min(n_g, int(ceilf(float32(n_g) * float32(ratio)))):
+
+            k     : m_max = min(max_nodes, B * k)
+            ratio : m_max = min(max_nodes, ceil(float32(ratio) * max_nodes * (1 + 2^-22)) + B)      (evaluated exactly)
+
+        (each float32 product is at most the exact one times 1 + 2^-22, each ceil adds less than 1, there are at most B live
+        graphs, and the live nodes are within max_nodes: DESIGN.md §2.27).  ValueError: both or neither of k / ratio, a
+        negative or non-finite value, a k that is no integer, sizes beyond int32."""
+        import fractions
+        import math
+        cap = self.capacities
+        if (k is None) == (ratio is None):
+            raise ValueError("pooled_capacities: give either k or ratio, {}".format(
+                "not both of them" if k is not None else "got neither"))
+        B = int(cap.batch_size)
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+                raise ValueError("pooled_capacities: k must be an integer of at least 0, got {!r}".format(k))
+            if int(k) >= (1 << 31) - 1:
+                raise ValueError("pooled_capacities: k = {} does not fit int32".format(k))
+            m_max = min(int(cap.max_nodes), B * int(k))
+        else:
+            if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)):
+                raise ValueError("pooled_capacities: ratio must be a number of at least 0, got {!r}".format(ratio))
+            r32 = float(np.float32(ratio))
+            if not (r32 >= 0.0) or math.isinf(r32):
+                raise ValueError("pooled_capacities: ratio must be a finite number of at least 0, got {!r}".format(ratio))
+            bound = fractions.Fraction(r32) * int(cap.max_nodes) * (1 + fractions.Fraction(1, 1 << 22))
+            m_max = min(int(cap.max_nodes), math.ceil(bound) + B)
+        if m_max + int(cap.sinks) >= (1 << 31) - 1:
+            raise ValueError("pooled_capacities: {} kept nodes + {} sinks do not fit int32".format(m_max, cap.sinks))
+        return type(cap)(B, m_max, cap.max_edges, cap.sink_degree, cap.sinks, m_max + cap.sinks, cap.e_cap)
+
     def check(self):
         """The ONE host read of a static batch, when the caller wants it: ValueError naming the first id outside [-1, G), or
-        the first slot dropped because the batch would exceed max_nodes / max_edges.  Either slot is dead in this batch."""
+        the first slot dropped because the batch would exceed max_nodes / max_edges.  Either slot is dead in this batch.  A
+        pooled batch (nn.sag_pool_static) carries its parent's flags on, so it names the same slot; its own two flags — kept
+        nodes beyond its capacities, a graph longer than the selection's cap — are named too."""
         B = self.num_slots
         host = torch.cat([self.counts[3:4].long(), self._given_ids.reshape(-1).long(), self.graph_mask.long()]).cpu().numpy()      # the one read
         flags, ids, mask = int(host[0]), host[1:1 + B], host[1 + B:] != 0
         if flags == 0:
             return self
+        if flags & L.STATIC_POOL_TOO_LONG:
+            raise ValueError("sag_pool_static: a graph of the batch has more than {} nodes (TFGX_STATIC_POOL_MAX_GRAPH_NODES) "
+                             "and kept none".format(L.STATIC_POOL_MAX_GRAPH_NODES))
+        if flags & L.STATIC_POOL_CLAMPED:
+            raise ValueError("sag_pool_static: the kept nodes exceeded max_nodes = {} of the pooled capacities and were cut "
+                             "off: the capacities were not made by pooled_capacities for this k / ratio".format(
+                                 self.capacities.max_nodes))
         if flags & L.COLLATE_STATIC_BAD_ID:
             bad = np.nonzero((ids < -1) | (ids >= self._store_len))[0]
             raise ValueError("collate_static: graph id {} (slot {} of the batch) is outside [0, {}) and is not -1".format(

@@ -301,6 +301,12 @@ class GraphStore(object):
             self._degrees = tuple(int(np.bincount(ei[k], minlength=1).max()) if ei.shape[1] and n else 0 for k in (0, 1))
         return self._degrees
 
+    def _max_graph_nodes(self):
+        """The node count of the store's largest graph: host work, once (nn.sag_pool_static holds it to the selection's cap)."""
+        if getattr(self, "_largest_graph", None) is None:
+            self._largest_graph = int(np.diff(self.node_ptr).max(initial=0))
+        return self._largest_graph
+
     def _static_ids(self, ids, dev):
         """int32 ids on the device without a read: an id wider than int32 is clamped to an out-of-range int32 first (the
         kernel then flags it as it flags any other)."""
@@ -411,6 +417,7 @@ class GraphStore(object):
             else:
                 y = d["y"].new_zeros((B,) + tuple(d["y"].shape[1:]))
         batch = StaticBatchGraph(x, ei, ngi, egi, y, w, ids, mask, counts, cap, G, given_ids=given)
+        batch._store, batch.graph_row_ptr = self, graph_row_ptr
         plan, plan_t = plans
         plan._edge_index = ei
         plan._transposed, plan_t._transposed = plan_t, plan

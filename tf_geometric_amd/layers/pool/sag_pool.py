@@ -3,6 +3,7 @@
 inputs = [x, edge_index, edge_weight, node_graph_index] -> [pooled_x, pooled_edge_index, pooled_edge_weight,
 pooled_node_graph_index]."""
 from ...nn.pool.sag_pool import sag_pool
+from ...nn.pool.sag_pool_static import sag_pool_static
 from ...nn.pool.sort_pool import sort_pool
 from .._base import Layer
 
@@ -32,6 +33,12 @@ class SAGPool(Layer):
         x, edge_index, edge_weight, node_graph_index = inputs
         return sag_pool(x, edge_index, edge_weight, node_graph_index, self.score_gnn, k=self.k, ratio=self.ratio,
                         score_activation=self.score_activation, training=training, cache=cache)
+
+    def pool_static(self, x, batch, training=None, capacities=None):
+        """The layer on a StaticBatchGraph (GraphStore.collate_static's, or an earlier pool_static's): the pooled
+        StaticBatchGraph of nn.sag_pool_static with this layer's k / ratio / activation.  No host read; capturable."""
+        return sag_pool_static(x, batch, self.score_gnn, k=self.k, ratio=self.ratio, score_activation=self.score_activation,
+                               training=training, capacities=capacities)
 
 
 class SortPool(Layer):

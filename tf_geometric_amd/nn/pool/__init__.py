@@ -2,6 +2,7 @@
 from .common_pool import mean_pool, sum_pool, max_pool, min_pool
 from .topk_pool import topk_pool
 from .sag_pool import sag_pool
+from .sag_pool_static import sag_pool_static, topk_pool_static
 from .sort_pool import sort_pool
 from .set2set import set2set
 from .cluster_pool import cluster_pool
