@@ -12,7 +12,12 @@ have the capacity (batch, fan-outs) give, the short last batch of an epoch fills
 is masked with mb.seed_mask; nothing is read back from the device.  --capture replays that whole step — sample, forward,
 backward, Adam — from one hipGraph (tfg.CapturedTrainStep); the sampling seed is a device word the captured step advances.
 
+--half-features bf16 | fp16 keeps the feature table in 16 bits (tfg.prepare_half_features(..., minibatch=True), on its line-friendly
+row stride) and drops the float32 copy: the gather and the fused input hop read it in place (include/tfgx_minibatch_h16.h) and
+return float32 rows, bit for bit what they return for the table widened to float32.  It composes with every flag above.
+
     python examples/demo_graph_sage_minibatch.py [--epochs 5] [--batch 256] [--fuse-input-hop] [--static | --capture]
+                                                 [--half-features bf16|fp16]
 """
 import argparse
 import os
@@ -27,15 +32,19 @@ from tf_geometric_amd.synthetic import planted_partition_graph   # noqa: E402
 from tf_geometric_amd.utils import RandomNeighborSampler   # noqa: E402
 
 FANOUTS = [25, 10]               # fanouts[l] belongs to layer l, input side first
+HALF_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
-def main(epochs=5, batch=256, num_nodes=20000, classes=6, quiet=False, fuse_input_hop=False, static=False, capture=False):
+def main(epochs=5, batch=256, num_nodes=20000, classes=6, quiet=False, fuse_input_hop=False, static=False, capture=False,
+         half_features=None):
     static = static or capture
     torch.manual_seed(0)
     x_np, ei_np, y_np = planted_partition_graph(num_nodes, classes=classes, degree=12, features=32, seed=0)
     # extra feature noise: a node's own row says little about its class, the mean over its (mostly same-class) neighbours does
     x_np = x_np + 3.0 * np.random.Generator(np.random.PCG64(1)).standard_normal(x_np.shape).astype(np.float32)
     x, y = tfg._lib.as_f32(x_np), torch.from_numpy(y_np).to(tfg._lib.device())
+    if half_features is not None:                                    # the table every step gathers from, in 16 bits from here on
+        x = tfg.prepare_half_features(x, HALF_DTYPES[half_features], minibatch=True)
     sampler = RandomNeighborSampler(tfg._lib.as_i32(ei_np))          # device tensors in -> device tensors out
     perm = torch.randperm(num_nodes)
     train_ids, test_ids = perm[:num_nodes * 4 // 5], perm[num_nodes * 4 // 5:]
@@ -124,6 +133,8 @@ if __name__ == "__main__":
     ap.add_argument("--fuse-input-hop", action="store_true", help="draw and reduce the outermost hop in one launch")
     ap.add_argument("--static", action="store_true", help="fixed-shape sampling: no host read, dead slots, a masked loss")
     ap.add_argument("--capture", action="store_true", help="--static, the whole step replayed from one hipGraph")
+    ap.add_argument("--half-features", choices=sorted(HALF_DTYPES), default=None,
+                    help="keep the feature table in 16 bits; the gather and the fused input hop read it in place")
     args = ap.parse_args()
     main(epochs=args.epochs, batch=args.batch, fuse_input_hop=args.fuse_input_hop, static=args.static or args.capture,
-         capture=args.capture)
+         capture=args.capture, half_features=args.half_features)

@@ -23,7 +23,7 @@ from .data import Graph, BatchGraph
 from .graph_capture import CapturedForward, CapturedTrainStep
 
 
-def prepare_half_features(x, dtype=_torch.bfloat16, gemm_operand=False, ld=None):
+def prepare_half_features(x, dtype=_torch.bfloat16, gemm_operand=False, ld=None, minibatch=False):
     """Store a float32 feature table in 16 bits (torch.bfloat16 by default, or torch.float16) for the aggregation kernels:
     a HalfRows on the line-friendly row stride (or on `ld` elements), quantised by tfgx_rows_f32_to_h16 (round to nearest
     even).  Arithmetic stays float32; the result of every reduce over it equals the float32 route's on
@@ -35,8 +35,12 @@ def prepare_half_features(x, dtype=_torch.bfloat16, gemm_operand=False, ld=None)
     choice and nothing falls back to a widened copy behind it.  Measured (tools/bench_gemm_half.py): on no
     shape is reading the table behind widening it first (1.25x to 7x ahead); against a float32 copy that is already held, the
     narrow-output (skinny) route is 34-38 % faster, the row kernel level, and the LDS-staged kernel slower — 233 k x 602 -> 64
-    by 22 %, -> 256 by 7 %."""
-    return HalfRows.from_dense(x, dtype=dtype, ld=ld, gemm_operand=gemm_operand)
+    by 22 %, -> 256 by 7 %.
+
+    minibatch=True declares the table for the minibatch route (include/tfgx_minibatch_h16.h): RandomNeighborSampler.sample_reduce
+    and the gather / input_aggregate of SampledMinibatch and StaticMinibatch then read it in place and return float32 rows — the
+    float32 route's bits on half_features_to_f32(h), with no float32 copy of the table.  Without the flag they refuse it."""
+    return HalfRows.from_dense(x, dtype=dtype, ld=ld, gemm_operand=gemm_operand, minibatch=minibatch)
 
 
 def half_features_to_f32(h):

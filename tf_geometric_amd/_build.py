@@ -37,15 +37,17 @@ def build(force=False, verbose=True):
     collate_hdr = os.path.join(CSRC, "tfgx_collate_tiles.h")   # the per-element bodies both collate kernels are compiled from
     host_hdr = os.path.join(CSRC, "tfgx_host.h")               # the refusals and workspace layouts of the entry points
     topk_hdr = os.path.join(CSRC, "tfgx_topk_keys.h")          # the score key and the node_k rule both selections share
-    own_deps = {"tfgx_reduce_h16.hip": [h16_hdr],
+    widen_hdr = os.path.join(CSRC, "tfgx_widen_h16.h")         # widening a 16-byte vector of a 16-bit table: every kernel that reads one
+    mb_h16_hdrs = [widen_hdr, h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_minibatch_h16.h")]
+    own_deps = {"tfgx_reduce_h16.hip": [h16_hdr, widen_hdr],
                 "tfgx_misc.hip": [sample_hdr],
                 "tfgx_plan.hip": [host_hdr], "tfgx_plan_ext.hip": [host_hdr], "tfgx_subgraph.hip": [host_hdr],
                 "tfgx_topk.hip": [host_hdr, topk_hdr], "tfgx_poolgrad.hip": [host_hdr],
                 "tfgx_nbrblock.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
                 "tfgx_samplereduce.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
-                                          os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
+                                          os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")] + mb_h16_hdrs,
                 "tfgx_nbrstatic.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h"),
-                                       os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")],
+                                       os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")] + mb_h16_hdrs,
                 "tfgx_gemm.hip": gemm_hdrs,
                 "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
                 "tfgx_fused.hip": fused_hdrs,
@@ -228,7 +230,8 @@ def build_asan(force=False, verbose=True):
     os.makedirs(ASAN_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC, x) for x in SOURCES]
     deps = srcs + [os.path.join(CSRC, "tfgx_common.h"), os.path.join(CSRC, "tfgx_sample_rows.h"),
-                   os.path.join(CSRC, "tfgx_host.h"), os.path.join(_HERE, "..", "include", "tfgx.h")]
+                   os.path.join(CSRC, "tfgx_host.h"), os.path.join(CSRC, "tfgx_widen_h16.h"),
+                   os.path.join(_HERE, "..", "include", "tfgx.h")]
     if not force and os.path.exists(ASAN_LIB) and not any(_newer(d, ASAN_LIB) for d in deps):
         return ASAN_LIB
     flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",

@@ -458,6 +458,17 @@ NBRSTATIC_SIGNATURES = {
                                                     _P, _P, _P]),
 }
 
+# include/tfgx_minibatch_h16.h (the minibatch route over a 16-bit feature table: the fused input hop in both forms, the gather)
+MINIBATCH_H16_ABI_VERSION = 1
+MINIBATCH_H16_SIGNATURES = {
+    "tfgx_minibatch_h16_version": (ctypes.c_int, []),
+    "tfgx_sample_reduce_h16": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I32, _I32, _U64, _P, _I64, _I64, _I32, _I32, _P, _I64, _P,
+                                              _P, _P]),
+    "tfgx_nbr_static_input_hop_h16": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I64, _I32, _I32, _P,
+                                                     _I64, _P, _P, _P]),
+    "tfgx_gather_rows_h16_f32": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I64, _P, _I64, _P]),
+}
+
 # include/tfgx_collate_static.h (fixed-shape batches: device-resident ids, capacities the host knows, no reads)
 COLLATE_STATIC_ABI_VERSION = 1
 COLLATE_STATIC_DEAD = -1             # TFGX_STATIC_BATCH_DEAD: a dead slot of the id list
@@ -518,6 +529,7 @@ ABIS = (
     Abi("tfgx_nbrblock.h", "tfgx_nbrblock_version", NBRBLOCK_ABI_VERSION, NBRBLOCK_SIGNATURES, ()),
     Abi("tfgx_samplereduce.h", "tfgx_samplereduce_version", SAMPLEREDUCE_ABI_VERSION, SAMPLEREDUCE_SIGNATURES, ()),
     Abi("tfgx_nbrstatic.h", "tfgx_nbrstatic_version", NBRSTATIC_ABI_VERSION, NBRSTATIC_SIGNATURES, ()),
+    Abi("tfgx_minibatch_h16.h", "tfgx_minibatch_h16_version", MINIBATCH_H16_ABI_VERSION, MINIBATCH_H16_SIGNATURES, ()),
     Abi("tfgx_collate_static.h", "tfgx_static_batch_version", COLLATE_STATIC_ABI_VERSION, COLLATE_STATIC_SIGNATURES, ()),
     Abi("tfgx_pool_static.h", "tfgx_static_pool_version", STATIC_POOL_ABI_VERSION, STATIC_POOL_SIGNATURES, ()),
 )

@@ -15,12 +15,14 @@
 //   finish  : row positions of the sampled edges (a binary search in block_row_ptr), the tail self-loops on the sinks with unit
 //             weights, block_row_ptr past R in closed form, -1 for the unused slots and the sinks of `node`, counts[0].
 // The other entry of the header, tfgx_nbrstatic_input_hop_f32, is the seed-pointer form of samplereduce_kernel and lives in
-// tfgx_samplereduce.hip.
+// tfgx_samplereduce.hip.  The gather out of a 16-bit table (include/tfgx_minibatch_h16.h) sits next to the float32 one.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
 #include "tfgx_sample_rows.h"
+#include "tfgx_widen_h16.h"
 #include "../../include/tfgx_nbrblock.h"
 #include "../../include/tfgx_nbrstatic.h"
+#include "../../include/tfgx_minibatch_h16.h"
 
 namespace tfgx {
 namespace {
@@ -158,6 +160,30 @@ __global__ void gather_rows_kernel(const float* __restrict__ x, int64_t ldx, con
 #pragma unroll
         for (int e = 0; e < VEC; ++e) v[e] = id < 0 ? 0.0f : v[e];
         store_vec<VEC>(out + i * ldo + col0 + int64_t(c) * VEC, v);
+    }
+}
+
+// the same gather out of a 16-bit table (include/tfgx_minibatch_h16.h): a lane per (row, 16-byte chunk of 8 elements), widened in
+// registers and stored as float32; the last chunk reads the row's pad columns and stores only the columns below F
+template <int DT>
+__global__ void gather_rows_h16_kernel(const uint16_t* __restrict__ x, int64_t ldx, const int32_t* __restrict__ idx, int64_t M,
+                                       int F, int nchunks, float* __restrict__ out, int64_t ldo, int out_vec)
+{
+    int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t total = M * nchunks;
+    for (; t < total; t += stride) {
+        const int64_t i = t / nchunks;
+        const int c = int(t - i * nchunks);
+        const int32_t id = idx[i];
+        const int64_t row = id < 0 ? 0 : id;
+        uint4 raw = *reinterpret_cast<const uint4*>(x + row * ldx + int64_t(c) * kVec);
+        asm volatile("" : "+v"(raw.x), "+v"(raw.y), "+v"(raw.z), "+v"(raw.w));
+        float v[kVec];
+        widen8<DT>(raw, v);
+#pragma unroll
+        for (int e = 0; e < kVec; ++e) v[e] = id < 0 ? 0.0f : v[e];
+        store8_f32(out + i * ldo + int64_t(c) * kVec, out_vec != 0, min(kVec, F - c * kVec), v);
     }
 }
 
@@ -364,5 +390,34 @@ extern "C" int tfgx_nbrstatic_gather_rows_f32(const float* x, int64_t ldx, const
         gather_rows_kernel<1><<<grid_for(M * F, kBlock), kBlock, 0, stream>>>(x, ldx, idx, M, 0, int(F), out, ldo);
         TFGX_LAUNCH_CHECK("gather_rows_kernel<1>");
     }
+    return TFGX_OK;
+}
+
+// include/tfgx_minibatch_h16.h: the gather of both minibatch classes out of a 16-bit table (its other entries, the fused input
+// hop over such a table, live in tfgx_samplereduce.hip)
+extern "C" int tfgx_gather_rows_h16_f32(const void* x, int64_t ldx, int32_t x_dtype, const int32_t* idx, int64_t M, int64_t F,
+                                        float* out, int64_t ldo, tfgx_stream_t stream_)
+{
+    TFGX_RANGE();
+    hipStream_t stream = as_stream(stream_);
+    if (!is_h16(x_dtype)) return bad_arg(__func__, "x_dtype must be TFGX_DT_BF16 or TFGX_DT_F16", x_dtype);
+    if (int rc = check_size(__func__, "M", M)) return rc;
+    if (F < 1) return bad_arg(__func__, "F must be at least 1", (long long)F);
+    if (int rc = check_size(__func__, "F", F)) return rc;
+    if (ldx < F) return bad_arg(__func__, "ldx must be at least F", (long long)ldx);
+    if (ldx % kVec != 0) return bad_arg(__func__, "ldx must be a multiple of 8: rows of a 16-bit table are 16-byte aligned", (long long)ldx);
+    if (!aligned_to(x, 16)) return bad_arg(__func__, "x must be 16-byte aligned: its address modulo 16", (long long)(reinterpret_cast<uintptr_t>(x) % 16));
+    if (ldo < F) return bad_arg(__func__, "ldo must be at least F", (long long)ldo);
+    if (M == 0) return TFGX_OK;
+    if (x == nullptr) return null_arg(__func__, "x");
+    if (idx == nullptr) return null_arg(__func__, "idx");
+    if (out == nullptr) return null_arg(__func__, "out");
+    const int nchunks = int((F + kVec - 1) / kVec);
+    const int out_vec = (ldo % 4 == 0 && aligned_to(out, 16)) ? 1 : 0;
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    const int grid = grid_for(M * nchunks, kBlock);
+    if (x_dtype == TFGX_DT_BF16) gather_rows_h16_kernel<TFGX_DT_BF16><<<grid, kBlock, 0, stream>>>(xh, ldx, idx, M, int(F), nchunks, out, ldo, out_vec);
+    else gather_rows_h16_kernel<TFGX_DT_F16><<<grid, kBlock, 0, stream>>>(xh, ldx, idx, M, int(F), nchunks, out, ldo, out_vec);
+    TFGX_LAUNCH_CHECK("gather_rows_h16_kernel");
     return TFGX_OK;
 }

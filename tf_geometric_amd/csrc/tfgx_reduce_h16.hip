@@ -14,6 +14,7 @@
 // elements per chunk whatever F is: the columns in [F, roundup8(F)) are inside the row stride, they are read and discarded.
 // This file copies what it needs from tfgx_reduce.hip on purpose: that file's code generation must not move.
 #include "tfgx_common.h"
+#include "tfgx_widen_h16.h"
 #include "../../include/tfgx_h16.h"
 #include <cfloat>
 #include <cstdio>
@@ -36,8 +37,6 @@ __device__ __forceinline__ float bcast_f(float v, int j)
     if constexpr (G == 64) return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
     else return __shfl(v, j, G);
 }
-
-constexpr int kVec = 8;      // elements per 16-byte vector of a 16-bit table
 
 struct HArgs {
     const int32_t* row_begin;
@@ -65,30 +64,8 @@ struct HArgs {
     int32_t wide_blocks;
 };
 
-// ---- 16-bit <-> fp32 in registers.  Widening is exact; narrowing is round-to-nearest-even, NaN stays NaN.
-template <int DT>
-__device__ __forceinline__ float widen1(uint32_t bits16)
-{
-    if constexpr (DT == TFGX_DT_BF16) return __uint_as_float(bits16 << 16);
-    else return float(__builtin_bit_cast(_Float16, static_cast<unsigned short>(bits16)));
-}
-
-template <int DT>
-__device__ __forceinline__ void widen8(const uint4 r, float (&v)[kVec])
-{
-    const uint32_t u[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if constexpr (DT == TFGX_DT_BF16) {
-            v[2 * i] = __uint_as_float(u[i] << 16);
-            v[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
-        } else {
-            v[2 * i] = widen1<DT>(u[i] & 0xFFFFu);
-            v[2 * i + 1] = widen1<DT>(u[i] >> 16);
-        }
-    }
-}
-
+// ---- 16-bit <-> fp32 in registers (widen1 / widen8: tfgx_widen_h16.h).  Widening is exact; narrowing is round-to-nearest-even,
+// NaN stays NaN.
 __device__ __forceinline__ float widen_rt(uint32_t bits16, int dt)
 {
     return dt == TFGX_DT_BF16 ? widen1<TFGX_DT_BF16>(bits16) : widen1<TFGX_DT_F16>(bits16);
@@ -115,20 +92,6 @@ __device__ __forceinline__ void load8_f32(const float* p, bool vec, int nv, floa
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[4 * h + i] = (4 * h + i < nv) ? p[4 * h + i] : 0.0f;
-        }
-    }
-}
-
-__device__ __forceinline__ void store8_f32(float* p, bool vec, int nv, const float (&v)[kVec])
-{
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (vec && nv >= 4 * h + 4) {
-            *reinterpret_cast<float4*>(p + 4 * h) = make_float4(v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (4 * h + i < nv) p[4 * h + i] = v[4 * h + i];
         }
     }
 }
@@ -507,8 +470,6 @@ __global__ __launch_bounds__(kBlock) void rows_h16_to_f32_kernel(const uint16_t*
         store8_f32(dst + i * ld_dst + j, dst_vec != 0, nv, v);
     }
 }
-
-inline bool is_h16(int32_t dt) { return dt == TFGX_DT_BF16 || dt == TFGX_DT_F16; }
 
 // The host checks both entry points share; fills the kernel arguments.
 int check_and_fill(const char* fn, const tfgx_reduce_args* p, int32_t x_dtype, int32_t out_dtype, HArgs* a)

@@ -353,9 +353,13 @@ class HalfRows(object):
     gemm_operand=True declares the table for the GEMM position as well: gemm_bias_act / gemm_tn and, through them, the
     GEMM-first layers (GCN with units <= F, GAT, the self half and the narrow route of mean / sum GraphSAGE) read it with
     tfgx_gemm_bias_act_cols_ws_h16 / tfgx_gemm_tn_gated_h16 (include/tfgx_gemm_h16.h) — the float32 GEMM's bits for .float(),
-    no widened copy.  Without it those layers refuse the table as before."""
+    no widened copy.  Without it those layers refuse the table as before.
 
-    def __init__(self, table, F, source=None, gemm_operand=False):
+    minibatch=True declares the table for the minibatch route (include/tfgx_minibatch_h16.h): RandomNeighborSampler.sample_reduce,
+    SampledMinibatch / StaticMinibatch.gather and .input_aggregate read it in place and return float32 — the bits of the float32
+    route on .float().  Without it those entry points refuse the table as before."""
+
+    def __init__(self, table, F, source=None, gemm_operand=False, minibatch=False):
         assert isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype in L.H16_DTYPES, \
             "HalfRows: a 2-D torch.bfloat16 / torch.float16 tensor"
         F = int(F)
@@ -370,6 +374,7 @@ class HalfRows(object):
         self.dtype, self.device = table.dtype, table.device
         self.source = source          # from_tensor: the caller's 16-bit tensor, which receives d/dx
         self.gemm_operand = bool(gemm_operand)
+        self.minibatch = bool(minibatch)
 
     @property
     def requires_grad(self):
@@ -391,7 +396,7 @@ class HalfRows(object):
         return HalfRows(torch.empty((int(n), ld), dtype=dtype, device=device), F)
 
     @staticmethod
-    def from_dense(x, dtype=torch.bfloat16, ld=None, out=None, gemm_operand=False):
+    def from_dense(x, dtype=torch.bfloat16, ld=None, out=None, gemm_operand=False, minibatch=False):
         """Quantise a float32 [n, F] tensor (tfgx_rows_f32_to_h16: round to nearest even) into `out` or a new table."""
         lib = L.require_gpu()
         if dtype not in L.H16_DTYPES:
@@ -401,12 +406,13 @@ class HalfRows(object):
         h = HalfRows.empty(n, F, dtype, x.device, ld) if out is None else out
         assert h.shape == (n, F) and h.dtype == dtype
         h.gemm_operand = h.gemm_operand or bool(gemm_operand)
+        h.minibatch = h.minibatch or bool(minibatch)
         L.check(lib.tfgx_rows_f32_to_h16(L.ptr(x), ldx, n, F, L.ptr(h.table), h.ld, L.H16_DTYPES[dtype], L.stream_ptr()),
                 "tfgx_rows_f32_to_h16")
         return h
 
     @staticmethod
-    def from_tensor(t, gemm_operand=False):
+    def from_tensor(t, gemm_operand=False, minibatch=False):
         """A HalfRows over a 16-bit torch tensor [n, F] that may require grad: autograd.aggregate on it hands t the float32
         gradient rounded to t.dtype.  The tensor itself is the table when its rows are 16-byte aligned, else its values are
         copied onto the friendly stride."""
@@ -421,7 +427,7 @@ class HalfRows(object):
             buf = torch.empty((n, h16_friendly_ld(F)), dtype=d.dtype, device=dev)
             buf[:, :F].copy_(d)
             d = buf
-        return HalfRows(d, F, source=t if t.requires_grad else None, gemm_operand=gemm_operand)
+        return HalfRows(d, F, source=t if t.requires_grad else None, gemm_operand=gemm_operand, minibatch=minibatch)
 
 
 def _h16_avg_lines(F, ld):

@@ -255,11 +255,13 @@ class RandomNeighborSampler(object):
         """The input hop of a minibatch in one launch (include/tfgx_samplereduce.h): float32 [len(rows), F] on the device, row i
         the `op` ("mean" / "sum") of w_j * x[c_j] over the neighbours (c_j, w_j) that sample_rows(rows, k=k, padding=padding,
         seed=seed) lists for node rows[i] — drawn and reduced on chip, no list, no gathered copy of x.  A row without
-        neighbours (or k = 0) is zeros.  x: a float32 table with a row for every node of the sampler's graph.
+        neighbours (or k = 0) is zeros.  x: a float32 table with a row for every node of the sampler's graph, or a HalfRows
+        declared minibatch=True (prepare_half_features(..., minibatch=True)), read in place by tfgx_sample_reduce_h16
+        (include/tfgx_minibatch_h16.h): the bits of this call on x.float().
         minibatch.sample_reduce_route(k, x) names the route: "fused" for 0 <= k <= _lib.SAMPLEREDUCE_MAX_DRAWS and an x that
         does not require grad (one host read: the verdict on `rows`); otherwise "composed" — sample_rows with the same seed,
-        then the reduction over that list, which carries d/dx.  k=None and ratio= have no fused form: ValueError.  A HalfRows:
-        TypeError.  An id outside the graph, or an x with too few rows: ValueError.  Refused inside a hipGraph capture.
+        then the reduction over that list, which carries d/dx.  k=None and ratio= have no fused form: ValueError.  A HalfRows
+        that was not declared, or a 16-bit tensor: TypeError.  An id outside the graph, or an x with too few rows: ValueError.  Refused inside a hipGraph capture.
         out=: a float32 [len(rows), F] tensor with dense rows (a column block of a wider buffer) to write into;
         return_count=True returns (out, int32 [len(rows)] draws per row)."""
         from .minibatch import sample_reduce

@@ -12,7 +12,11 @@ The outermost hop's ids are consumed once, by layer 0's neighbour reduction: Ran
 
 sample_blocks reads its sizes back (L + 1 host reads) and cannot be captured.  RandomNeighborSampler.sample_blocks_static
 (include/tfgx_nbrstatic.h) is the same sample padded to capacities the host knows from (len(seeds), fanouts): no read, a fixed
-launch sequence, replayable from a hipGraph."""
+launch sequence, replayable from a hipGraph.
+
+Every entry point here that reads the feature table takes a float32 table or a 16-bit one declared for this route
+(prepare_half_features(..., minibatch=True); include/tfgx_minibatch_h16.h) and returns float32: for the 16-bit table, bit for bit
+what it returns for the table widened to float32."""
 import collections
 
 import numpy as np
@@ -73,7 +77,8 @@ class SampledMinibatch(object):
     def input_aggregate(self, x, op="mean"):
         """The outermost hop, drawn and reduced in one launch: float32 [len(node_index), F], row i the `op` ("mean" / "sum")
         over the neighbours node node_index[i] draws with the recorded (k, padding, seed) — what the unfused call's blocks[0]
-        reduces from gather(x).  No host read: the ids are the sampler's own."""
+        reduces from gather(x).  No host read: the ids are the sampler's own.  x: a float32 table, or a HalfRows declared
+        minibatch=True (the bits of the call on x.float())."""
         if self.input_hop is None:
             raise ValueError("input_aggregate needs a minibatch of sample_blocks(..., fuse_input_hop=True)")
         k, padding, seed = self.input_hop
@@ -81,7 +86,12 @@ class SampledMinibatch(object):
 
     def gather(self, x):
         """x[node_index] for a float32 feature table [N, F] (tfgx_gather_rows_f32; a table that is being trained goes through
-        torch's indexing, which carries the gradient)."""
+        torch's indexing, which carries the gradient), or for a HalfRows declared minibatch=True: its rows widened to float32
+        (tfgx_gather_rows_h16_f32), the bits of gather(x.float())."""
+        half = _half_table(x, "SampledMinibatch.gather")
+        if half is not None:
+            n_nodes = _state(self._sampler).n_nodes if self._sampler is not None else 0
+            return _gather_half(half, self.node_index, n_nodes, "SampledMinibatch.gather")
         if isinstance(x, torch.Tensor):
             if x.dtype != torch.float32:
                 raise TypeError("SampledMinibatch.gather takes a float32 table, got {}".format(x.dtype))
@@ -135,6 +145,40 @@ def _table(x, n_nodes, who):
         raise ValueError("{}: x has {} rows but the sampler's graph has {} nodes".format(who, int(x.shape[0]), n_nodes))
     x2, ldx = L.row_major_2d(x)
     return x2, ldx, int(x.shape[1])
+
+
+def _half_table(x, who):
+    """x as a 16-bit table of the minibatch route (include/tfgx_minibatch_h16.h): the HalfRows when it was declared
+    minibatch=True, None for anything that is no HalfRows (the float32 path judges it), TypeError for an undeclared one."""
+    from ..plan import HalfRows
+    if not isinstance(x, HalfRows):
+        return None
+    if not x.minibatch:
+        raise TypeError("{} takes a float32 table, got a HalfRows that was not declared for the minibatch route: make it with "
+                        "prepare_half_features(..., minibatch=True) / HalfRows(..., minibatch=True), or pass x.float()".format(who))
+    return x
+
+
+def _half_args(h, n_nodes, who):
+    """(the table, its leading dimension in elements, F, TFGX_DT_*) of a declared HalfRows, with the float32 route's refusal of a
+    table shorter than the graph."""
+    if int(h.shape[0]) < n_nodes:
+        raise ValueError("{}: x has {} rows but the sampler's graph has {} nodes".format(who, int(h.shape[0]), n_nodes))
+    return h.table, h.ld, h.F, L.H16_DTYPES[h.dtype]
+
+
+def _gather_half(h, idx, n_nodes, who):
+    """float32 [len(idx), F] = widen(h[idx]), zeros where idx < 0 (tfgx_gather_rows_h16_f32): no host read."""
+    if h.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("{}: a HalfRows whose source requires grad has no gather that carries the gradient (a trained "
+                                  "16-bit table is out of scope): gather from a float32 tensor that requires grad".format(who))
+    lib = L.require_gpu()
+    table, ld, F, dt = _half_args(h, n_nodes, who)
+    M = int(idx.shape[0])
+    out = torch.empty((M, F), dtype=torch.float32, device=table.device)
+    L.check(lib.tfgx_gather_rows_h16_f32(L.ptr(table), ld, dt, L.ptr(idx), M, F, L.ptr(out), F, L.stream_ptr()),
+            "tfgx_gather_rows_h16_f32")
+    return out
 
 
 class _State(object):
@@ -285,10 +329,11 @@ def check_sample_reduce_args(k, ratio=None):
 
 
 def sample_reduce_route(k, x):
-    """"fused" (one launch of tfgx_samplereduce_f32) or "composed" (sample_rows, then the reduction over the list, which
-    carries d/dx): what sample_reduce itself dispatches on."""
+    """"fused" (one launch of tfgx_samplereduce_f32, or of tfgx_sample_reduce_h16 for a HalfRows) or "composed" (sample_rows,
+    then the reduction over the list, which carries d/dx): what sample_reduce itself dispatches on."""
     check_sample_reduce_args(k)
-    trained = isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+    # a torch.Tensor, or a HalfRows (whose source tensor receives d/dx)
+    trained = bool(getattr(x, "requires_grad", False)) and torch.is_grad_enabled()
     return "fused" if int(k) <= L.SAMPLEREDUCE_MAX_DRAWS and not trained else "composed"
 
 
@@ -300,21 +345,23 @@ def _check_out(out, n_rows, F, dev):
 
 def sample_reduce(sampler, rows, x, k, op="mean", padding=False, seed=None, ratio=None, out=None, return_count=False,
                   _own_ids=False):
-    from ..plan import CsrPlan, HalfRows, segment_reduce
+    from ..plan import CsrPlan, segment_reduce
     check_sample_reduce_args(k, ratio)
     if op not in _OPS:
         raise ValueError("sample_reduce: op must be 'mean' or 'sum', got {!r}".format(op))
-    if isinstance(x, HalfRows):
-        raise TypeError("sample_reduce takes a float32 table, got a HalfRows (16-bit tables are out of scope here: pass x.float())")
+    half = _half_table(x, "sample_reduce")
     if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
         raise TypeError("sample_reduce takes a float32 table, got {}".format(x.dtype))
     _check_ids(rows, "rows")
     lib = L.require_gpu()
     refuse_capture("RandomNeighborSampler.sample_reduce")
     route = sample_reduce_route(k, x)
-    x = L.as_f32(x)
     st = _state(sampler)
-    x2, ldx, F = _table(x, st.n_nodes, "sample_reduce")
+    if half is not None:        # a declared 16-bit table, read in place (include/tfgx_minibatch_h16.h)
+        x2, ldx, F, x_dt = _half_args(half, st.n_nodes, "sample_reduce")
+    else:
+        x = L.as_f32(x)
+        x2, ldx, F = _table(x, st.n_nodes, "sample_reduce")
     if seed is None:
         seed = _fresh_seed()
     dev = st.table.device
@@ -349,10 +396,16 @@ def sample_reduce(sampler, rows, x, k, op="mean", padding=False, seed=None, rati
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     if wide_bad is not None:
         flag |= wide_bad
-    L.check(lib.tfgx_samplereduce_f32(
-        L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(rows_t), n_rows, int(k),
-        1 if padding else 0, int(seed), L.ptr(x2), ldx, F, _OPS[op], L.ptr(out), ldo, L.ptr(count), L.ptr(flag), L.stream_ptr()),
-        "tfgx_samplereduce_f32")
+    if half is not None:
+        L.check(lib.tfgx_sample_reduce_h16(
+            L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(rows_t), n_rows, int(k),
+            1 if padding else 0, int(seed), L.ptr(x2), ldx, F, x_dt, _OPS[op], L.ptr(out), ldo, L.ptr(count), L.ptr(flag),
+            L.stream_ptr()), "tfgx_sample_reduce_h16")
+    else:
+        L.check(lib.tfgx_samplereduce_f32(
+            L.ptr(st.row_ptr), L.ptr(sampler.plan.col), L.ptr(sampler.w_csr), st.n_nodes, L.ptr(rows_t), n_rows, int(k),
+            1 if padding else 0, int(seed), L.ptr(x2), ldx, F, _OPS[op], L.ptr(out), ldo, L.ptr(count), L.ptr(flag),
+            L.stream_ptr()), "tfgx_samplereduce_f32")
     # the one host read: the verdict on `rows` (not taken for ids the sampler produced itself)
     if not _own_ids and int(flag.item()) != 0:
         raise ValueError("sample_reduce: a row id is outside [0, {})".format(st.n_nodes))
@@ -542,7 +595,11 @@ class StaticMinibatch(object):
 
     def gather(self, x):
         """float32 [R_L, F]: x[node_index] for the live rows, zeros for the dead ones (tfgx_nbrstatic_gather_rows_f32; a table
-        that is being trained goes through torch's indexing with a clamp and a mask, which carries the gradient)."""
+        that is being trained goes through torch's indexing with a clamp and a mask, which carries the gradient).  A HalfRows
+        declared minibatch=True is widened as it is gathered (tfgx_gather_rows_h16_f32): the bits of gather(x.float())."""
+        half = _half_table(x, "StaticMinibatch.gather")
+        if half is not None:
+            return _gather_half(half, self.node_index, self._n_nodes, "StaticMinibatch.gather")
         if isinstance(x, torch.Tensor):
             if x.dtype != torch.float32:
                 raise TypeError("StaticMinibatch.gather takes a float32 table, got {}".format(x.dtype))
@@ -561,21 +618,31 @@ class StaticMinibatch(object):
     def input_aggregate(self, x, op="mean"):
         """The outermost hop, drawn and reduced in one launch with the seed read from the device: float32 [len(node_index), F],
         row i the `op` ("mean" / "sum") over the neighbours node_index[i] draws — bit for bit what the dynamic minibatch's
-        input_aggregate gives that node — and zeros for a dead row.  No host read."""
+        input_aggregate gives that node — and zeros for a dead row.  No host read.  x: a float32 table, or a HalfRows declared
+        minibatch=True (tfgx_nbr_static_input_hop_h16: the bits of the call on x.float())."""
         if self.input_hop is None:
             raise ValueError("input_aggregate needs a minibatch of sample_blocks_static(..., fuse_input_hop=True)")
         if op not in _OPS:
             raise ValueError("input_aggregate: op must be 'mean' or 'sum', got {!r}".format(op))
+        half = _half_table(x, "StaticMinibatch.input_aggregate")
         if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
             raise _no_fused_static("takes a float32 table, got {}".format(x.dtype))
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        if bool(getattr(x, "requires_grad", False)) and torch.is_grad_enabled():      # a tensor, or a HalfRows over a trained one
             raise _no_fused_static("carries no gradient to a table that requires grad")
         lib = L.require_gpu()
         k, padding, hop = self.input_hop
         st = _state(self._sampler)
+        M = int(self.node_index.shape[0])
+        if half is not None:        # a declared 16-bit table, read in place (include/tfgx_minibatch_h16.h)
+            x2, ldx, F, x_dt = _half_args(half, st.n_nodes, "input_aggregate")
+            out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
+            L.check(lib.tfgx_nbr_static_input_hop_h16(
+                L.ptr(st.row_ptr), L.ptr(self._sampler.plan.col), L.ptr(self._sampler.w_csr), st.n_nodes, L.ptr(self.node_index), M,
+                int(k), 1 if padding else 0, L.ptr(self.seed), int(hop), L.ptr(x2), ldx, F, x_dt, _OPS[op], L.ptr(out), F, None,
+                L.ptr(self.flag), L.stream_ptr()), "tfgx_nbr_static_input_hop_h16")
+            return out
         x = L.as_f32(x)
         x2, ldx, F = _table(x, st.n_nodes, "input_aggregate")
-        M = int(self.node_index.shape[0])
         out = torch.empty((M, F), dtype=torch.float32, device=x2.device)
         L.check(lib.tfgx_nbrstatic_input_hop_f32(
             L.ptr(st.row_ptr), L.ptr(self._sampler.plan.col), L.ptr(self._sampler.w_csr), st.n_nodes, L.ptr(self.node_index), M,
