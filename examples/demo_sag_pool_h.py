@@ -181,11 +181,14 @@ def graph_store(data, indices):
     return tfg.data.GraphStore(graphs)
 
 
-def make_static_step(model, store, loader, capacities, opt, capture):
+def make_static_step(model, store, loader, capacities, opt, capture, loss=None):
     """step() -> the loss (a device scalar) of one training step on the loader's next batch.  capture=True records the step once
-    with tfg.CapturedTrainStep (opt must be capturable) and replays it."""
+    with tfg.CapturedTrainStep (opt must be capturable) and replays it.  loss(model, batch): static_loss when None (another
+    example's model brings its own: demo_sort_pool.py)."""
+    loss = static_loss if loss is None else loss
+
     def loss_fn():
-        return static_loss(model, store.collate_static(loader.next_ids(), capacities))
+        return loss(model, store.collate_static(loader.next_ids(), capacities))
 
     if not capture:
         def step():

@@ -15,7 +15,7 @@ SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
            "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip", "tfgx_collate_static.hip",
-           "tfgx_pool_static.hip"]
+           "tfgx_pool_static.hip", "tfgx_rows3d.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)
@@ -64,7 +64,10 @@ def build(force=False, verbose=True):
                 "tfgx_collate_static.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
                                             os.path.join(_HERE, "..", "include", "tfgx_collate_static.h")],
                 "tfgx_pool_static.hip": [host_hdr, topk_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
-                                         os.path.join(_HERE, "..", "include", "tfgx_pool_static.h")]}
+                                         os.path.join(_HERE, "..", "include", "tfgx_pool_static.h")],
+                "tfgx_rows3d.hip": [host_hdr, topk_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
+                                    os.path.join(_HERE, "..", "include", "tfgx_pool_static.h"),
+                                    os.path.join(_HERE, "..", "include", "tfgx_rows3d.h")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

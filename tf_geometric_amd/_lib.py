@@ -509,6 +509,15 @@ STATIC_POOL_SIGNATURES = {
     "tfgx_static_pool_gather_scale_rows_f32": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _P]),
 }
 
+# include/tfgx_rows3d.h (node rows -> the dense [G, k, F] tensor: convert_x_to_3d and the fused SortPool readout, one launch)
+ROWS3D_ABI_VERSION = 1
+ROWS3D_TOO_LONG = STATIC_POOL_TOO_LONG      # TFGX_ROWS3D_TOO_LONG: the flag word of a sort-mode call, ORed into counts[3]
+ROWS3D_MAX_GRAPH_NODES = STATIC_POOL_MAX_GRAPH_NODES      # the longest graph the sort mode ranks in LDS
+ROWS3D_SIGNATURES = {
+    "tfgx_rows3d_version": (ctypes.c_int, []),
+    "tfgx_segment_rows_3d_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry ("Adding a header").
@@ -532,6 +541,7 @@ ABIS = (
     Abi("tfgx_minibatch_h16.h", "tfgx_minibatch_h16_version", MINIBATCH_H16_ABI_VERSION, MINIBATCH_H16_SIGNATURES, ()),
     Abi("tfgx_collate_static.h", "tfgx_static_batch_version", COLLATE_STATIC_ABI_VERSION, COLLATE_STATIC_SIGNATURES, ()),
     Abi("tfgx_pool_static.h", "tfgx_static_pool_version", STATIC_POOL_ABI_VERSION, STATIC_POOL_SIGNATURES, ()),
+    Abi("tfgx_rows3d.h", "tfgx_rows3d_version", ROWS3D_ABI_VERSION, ROWS3D_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module

@@ -1193,6 +1193,51 @@ def gather_scale_static(x, idx, node_map, s=None):
     return _GatherScaleStatic.apply(x, s, idx, node_map)
 
 
+class _SegmentRows3D(torch.autograd.Function):
+    """Node rows -> the [G * k, F] rows of the dense [G, k, F] tensor (tfgx_segment_rows_3d_f32, one launch): the plain mode
+    (sort_col None: convert_x_to_3d) or the sort mode (SortPool's ranking by column sort_col of x).  Returns (out, slot_node,
+    flags).  The backward is one gather through node_slot (tfgx_static_pool_gather_scale_rows_f32 without a multiplier): every
+    row of dx is written once, as a copy or as zeros."""
+
+    @staticmethod
+    def forward(ctx, x, seg_ptr, seg_node, G, N, k, sort_col):
+        lib = L.require_gpu()
+        x2, ldx = L.row_major_2d(x)
+        n_rows, F = int(x2.shape[0]), int(x2.shape[1])
+        dev = x2.device
+        out = torch.empty((G * k, F), dtype=torch.float32, device=dev)
+        slot_node = torch.empty(G * k, dtype=torch.int32, device=dev)
+        node_slot = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+        key = None if sort_col is None else ctypes.c_void_p(x2.data_ptr() + 4 * int(sort_col))
+        L.check(lib.tfgx_segment_rows_3d_f32(L.ptr(seg_ptr), L.ptr(seg_node), G, N, L.ptr(x2), ldx, n_rows, F, k, key, ldx,
+                                             L.ptr(out), max(F, 1), L.ptr(slot_node), L.ptr(node_slot), L.ptr(flags),
+                                             L.stream_ptr()), "tfgx_segment_rows_3d_f32")
+        ctx.save_for_backward(node_slot)
+        ctx.slots, ctx.F = G * k, F
+        ctx.mark_non_differentiable(slot_node, flags)
+        return out, slot_node, flags
+
+    @staticmethod
+    def backward(ctx, g, _slot_node, _flags):
+        lib = L.require_gpu()
+        node_slot, = ctx.saved_tensors
+        n_rows, F = int(node_slot.shape[0]), ctx.F
+        if ctx.slots == 0 or n_rows == 0 or F == 0:
+            return (torch.zeros((n_rows, F), dtype=torch.float32, device=node_slot.device),) + (None,) * 6
+        g2, ldg = L.row_major_2d(g.to(torch.float32))
+        dx = torch.empty((n_rows, F), dtype=torch.float32, device=g2.device)
+        L.check(lib.tfgx_static_pool_gather_scale_rows_f32(L.ptr(g2), ldg, ctx.slots, L.ptr(node_slot), None, n_rows, F, L.ptr(dx),
+                                                           F, L.stream_ptr()), "tfgx_static_pool_gather_scale_rows_f32")
+        return (dx,) + (None,) * 6
+
+
+def segment_rows_3d(x, seg_ptr, seg_node, G, N, k, sort_col=None):
+    """(out [G * k, F], slot_node int32 [G * k], flags int32 [1]) of tfgx_segment_rows_3d_f32 over the graph plan (seg_ptr
+    int32 [G + 1], seg_node int32 [N] or None = the identity); differentiable wrt x.  sort_col: a column of x in [0, F)."""
+    return _SegmentRows3D.apply(x, seg_ptr, seg_node, int(G), int(N), int(k), sort_col)
+
+
 def gather_edge_values(w, edge_id):
     """w[edge_id] for a 1-D float32 tensor (tfgx_permute_rows_f32 with width 1)."""
     lib = L.require_gpu()

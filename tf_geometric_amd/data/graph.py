@@ -424,6 +424,13 @@ class StaticBatchGraph(BatchGraph):
         pooled = getattr(P, op + "_pool")(h, self.node_graph_index, self.num_graphs, cache=self.cache)[:self.num_slots]
         return torch.where(self.graph_mask[:, None], pooled, torch.zeros((), dtype=pooled.dtype, device=pooled.device))
 
+    def to_3d(self, h, k):
+        """[B, k, F]: utils.convert_x_to_3d of h ([n_cap, F]) over the slots — slot j of graph g is its j-th row, longer graphs
+        are cut off, the rest and every dead slot is exactly zero.  One launch over graph_row_ptr (the dead graph B and the
+        padded rows are never read), no host read."""
+        from ..nn.pool.sort_pool_3d import rows_3d_static
+        return rows_3d_static(h, self, k)
+
     def pooled_capacities(self, k=None, ratio=None):
         """StaticBatchCapacities of this batch pooled by nn.sag_pool_static(k= / ratio=): host arithmetic, no device.  The
         batch size, max_edges (kept edges are a subset of the live ones), the sink degree and the sinks P stay; max_nodes

@@ -246,6 +246,7 @@ class GraphStore(object):
         nodes = d["arange"][:n_out]
         from ..nn.pool.common_pool import CACHE_KEY_GRAPH_PLAN
         graph_plan = CsrPlan(tab[1], nodes, nodes, B, max(n_out, 1), n_out)
+        graph_plan._longest_row = int(np.diff(np.asarray(table[1])).max(initial=0))      # host arithmetic: nn.sort_pool_3d's route
         if n_out > 0:       # its flip has one edge per row, in row order: identity row_ptr and perm, col = the graph ids
             graph_plan._transposed = CsrPlan(d["arange"][:n_out + 1], ngi, nodes, n_out, B, n_out)
             graph_plan._transposed._transposed = graph_plan

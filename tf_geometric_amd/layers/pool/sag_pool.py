@@ -5,6 +5,7 @@ pooled_node_graph_index]."""
 from ...nn.pool.sag_pool import sag_pool
 from ...nn.pool.sag_pool_static import sag_pool_static
 from ...nn.pool.sort_pool import sort_pool
+from ...nn.pool.sort_pool_3d import sort_pool_3d, sort_pool_static
 from .._base import Layer
 
 
@@ -55,3 +56,19 @@ class SortPool(Layer):
         x, edge_index, edge_weight, node_graph_index = inputs
         return sort_pool(x, edge_index, edge_weight, node_graph_index, k=self.k, ratio=self.ratio,
                          sort_index=self.sort_index, training=training)
+
+    def pool_3d(self, inputs, num_graphs=None, cache=None):
+        """The DGCNN readout of this layer's k and sort_index: nn.sort_pool_3d, [num_graphs, k, F] in one launch, no pooled
+        edge list.  inputs = [x, node_graph_index], or the 4-list call() takes (its edges are not looked at)."""
+        if len(inputs) == 2:
+            x, node_graph_index = inputs
+        else:
+            x, _, _, node_graph_index = inputs
+        return sort_pool_3d(x, node_graph_index, k=self.k, sort_index=self.sort_index, num_graphs=num_graphs, cache=cache,
+                            ratio=self.ratio)
+
+    def pool_static(self, x, batch):
+        """The same readout on a StaticBatchGraph (nn.sort_pool_static): [B, k, F], no host read; capturable."""
+        if self.ratio is not None:
+            raise ValueError("SortPool.pool_static: ratio= has no 3-D form: construct the layer with k")
+        return sort_pool_static(x, batch, self.k, sort_index=self.sort_index)

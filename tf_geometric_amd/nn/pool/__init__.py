@@ -4,6 +4,7 @@ from .topk_pool import topk_pool
 from .sag_pool import sag_pool
 from .sag_pool_static import sag_pool_static, topk_pool_static
 from .sort_pool import sort_pool
+from .sort_pool_3d import sort_pool_3d, sort_pool_3d_route, sort_pool_static
 from .set2set import set2set
 from .cluster_pool import cluster_pool
 from .asap import asap

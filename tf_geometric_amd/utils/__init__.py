@@ -6,6 +6,7 @@ import torch
 
 from .. import _lib as L
 from .subgraph import compute_edge_mask_by_node_index, sample_new_graph_by_node_index
+from ..nn.pool.sort_pool_3d import convert_x_to_3d          # noqa: E402,F401 - utils/graph_utils.py:215-249
 from .link import (negative_sampling, negative_sampling_with_start_node, edge_train_test_split, extract_unique_edge,
                    convert_edge_index_to_edge_hash, convert_edge_hash_to_edge_index, sorted_adjacency)
 from .minibatch import (SampledMinibatch, SampledBlock, hop_seed, sample_reduce_route, StaticMinibatch, StaticCapacities,
