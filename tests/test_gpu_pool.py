@@ -72,13 +72,9 @@ def _np_induced(ei, keep, n):
     return np.stack([node_map[ei[0][mask]], node_map[ei[1][mask]]]).astype(np.int32), np.flatnonzero(mask)
 
 
-@pytest.mark.parametrize("n,e", [(1, 0), (50, 0), (200, 400), (3000, 12000), (2000, 80000), (70000, 300000)])
-def test_derived_plan_equals_rebuilt_plan(tfg, n, e):
-    """short rows (8 lanes a row) and long rows (a wave a row): row_ptr / col / perm bit-identical to CsrPlan.build of
-    the pooled edge list; the pooled list exact against the numpy restatement."""
+def _assert_induced_exact(tfg, ei, keep, n):
+    """the pooled list exact against the numpy restatement; the derived plan bit-identical to a rebuilt one"""
     from tf_geometric_amd.utils.subgraph import induced_subgraph
-    dev = torch.device("cuda")
-    ei, keep = _random_graph(n, e, seed=n + e, dev=dev)
     parent = tfg.CsrPlan.build(ei, n)
     sub = induced_subgraph(ei, keep, n, parent_plan=parent)
     ref_ei, ref_id = _np_induced(ei.cpu().numpy(), keep.cpu().numpy(), n)
@@ -88,6 +84,26 @@ def test_derived_plan_equals_rebuilt_plan(tfg, n, e):
     rebuilt = tfg.CsrPlan.build(sub.edge_index, m)
     for a in ("row_ptr", "col", "perm"):
         assert torch.equal(getattr(sub.plan, a), getattr(rebuilt, a)), a
+
+
+@pytest.mark.parametrize("n,e", [(1, 0), (50, 0), (200, 400), (3000, 12000), (2000, 80000), (70000, 300000),
+                                 (64, 2047), (64, 2048), (64, 2049), (700, 2049)])
+def test_derived_plan_equals_rebuilt_plan(tfg, n, e):
+    """short rows (8 lanes a row) and long rows (a wave a row): row_ptr / col / perm bit-identical to CsrPlan.build of
+    the pooled edge list; the pooled list exact against the numpy restatement.  E = 2047 / 2048 / 2049 are the edges of
+    the 2048-edge compaction tile: n = 64 walks a wave per row (E / n > 16), n = 700 eight lanes per row."""
+    ei, keep = _random_graph(n, e, seed=n + e, dev=torch.device("cuda"))
+    _assert_induced_exact(tfg, ei, keep, n)
+
+
+def test_derived_plan_keeps_no_node_then_every_node(tfg):
+    """n = 64, E = 2049 (a full tile and a tile of one edge): an empty node list keeps no edge, the whole node list
+    keeps every edge; both exact against the numpy restatement and a rebuilt plan."""
+    n, e = 64, 2049
+    dev = torch.device("cuda")
+    ei, _ = _random_graph(n, e, seed=n + e, dev=dev)
+    for m in (0, n):
+        _assert_induced_exact(tfg, ei, torch.arange(m, dtype=torch.int32, device=dev), n)
 
 
 def test_derived_plan_products_shape(tfg):

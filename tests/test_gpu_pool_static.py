@@ -34,7 +34,9 @@ BATCHES = {"B=1 the graph at the cap": [BIG],
            "B=4 all dead": [-1, -1, -1, -1],
            "B=4 small graphs": [NO_EDGES, 1, 2, 4],
            "B=9 dead first, in the middle and last, a graph twice": [-1, 7, 0, -1, 8, 9, 3, 3, -1],
-           "B=9 every boundary": [5, 6, BIG, -1, 9, 8, 7, 4, NO_EDGES]}
+           "B=9 every boundary": [5, 6, BIG, -1, 9, 8, 7, 4, NO_EDGES],
+           # more slots than the 1024 threads of the table and scan workgroups: every thread owns more than one
+           "B=1030 two slots a scan thread": [[10, 1, 2, 3, 4, -1][j % 6] for j in range(1030)]}
 SELECTIONS = (dict(k=1), dict(k=3), dict(k=1000), dict(ratio=0.0), dict(ratio=0.3), dict(ratio=0.5), dict(ratio=1.0), dict(ratio=1.5))
 _WORLD = {}
 

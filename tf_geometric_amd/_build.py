@@ -1,5 +1,6 @@
 # coding=utf-8
 """Builds tf_geometric_amd/lib/libtfgx.so (the C-ABI HIP library, gfx950 only) in-tree with hipcc."""
+import glob
 import os
 import subprocess
 import sys
@@ -25,54 +26,19 @@ def _newer(a, b):
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
+def _headers():
+    """Every header under csrc/ and include/: each is a dependency of every source, so a header edit rebuilds the library."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")))
+
+
 def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
-    deps = [os.path.join(CSRC, "tfgx_common.h"), os.path.join(_HERE, "..", "include", "tfgx.h")]
-    h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_h16.h")
-    fused_h16_hdr = os.path.join(_HERE, "..", "include", "tfgx_fused_h16.h")
-    # headers only some sources include (tfgx_fused_h16.h includes tfgx_h16.h)
-    fused_hdrs = [os.path.join(CSRC, "tfgx_fused_common.h"), os.path.join(CSRC, "tfgx_mfma.h")]
-    gemm_hdrs = [os.path.join(CSRC, "tfgx_gemm_kernels.h"), os.path.join(CSRC, "tfgx_mfma.h")]      # the GEMM templates both GEMM sources instantiate
-    sample_hdr = os.path.join(CSRC, "tfgx_sample_rows.h")      # the sampler's bodies and kernel pair: every sampler is compiled from it
-    collate_hdr = os.path.join(CSRC, "tfgx_collate_tiles.h")   # the per-element bodies both collate kernels are compiled from
-    host_hdr = os.path.join(CSRC, "tfgx_host.h")               # the refusals and workspace layouts of the entry points
-    topk_hdr = os.path.join(CSRC, "tfgx_topk_keys.h")          # the score key and the node_k rule both selections share
-    widen_hdr = os.path.join(CSRC, "tfgx_widen_h16.h")         # widening a 16-byte vector of a 16-bit table: every kernel that reads one
-    mb_h16_hdrs = [widen_hdr, h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_minibatch_h16.h")]
-    own_deps = {"tfgx_reduce_h16.hip": [h16_hdr, widen_hdr],
-                "tfgx_misc.hip": [sample_hdr],
-                "tfgx_plan.hip": [host_hdr], "tfgx_plan_ext.hip": [host_hdr], "tfgx_subgraph.hip": [host_hdr],
-                "tfgx_topk.hip": [host_hdr, topk_hdr], "tfgx_poolgrad.hip": [host_hdr],
-                "tfgx_nbrblock.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h")],
-                "tfgx_samplereduce.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_samplereduce.h"),
-                                          os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")] + mb_h16_hdrs,
-                "tfgx_nbrstatic.hip": [host_hdr, sample_hdr, os.path.join(_HERE, "..", "include", "tfgx_nbrblock.h"),
-                                       os.path.join(_HERE, "..", "include", "tfgx_nbrstatic.h")] + mb_h16_hdrs,
-                "tfgx_gemm.hip": gemm_hdrs,
-                "tfgx_gemm_h16.hip": gemm_hdrs + [h16_hdr, os.path.join(_HERE, "..", "include", "tfgx_gemm_h16.h")],
-                "tfgx_fused.hip": fused_hdrs,
-                "tfgx_fused_h16.hip": [h16_hdr, fused_h16_hdr] + fused_hdrs,
-                "tfgx_dropedge.hip": [host_hdr, os.path.join(_HERE, "..", "include", "tfgx_dropedge.h")],
-                "tfgx_linkpred.hip": [os.path.join(_HERE, "..", "include", "tfgx_linkpred.h")],
-                "tfgx_lstm.hip": [os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],
-                "tfgx_set2set.hip": [os.path.join(_HERE, "..", "include", "tfgx_set2set.h"),
-                                     os.path.join(_HERE, "..", "include", "tfgx_lstm.h")],
-                "tfgx_asap.hip": [host_hdr, os.path.join(_HERE, "..", "include", "tfgx_asap.h")],
-                "tfgx_seggram.hip": [os.path.join(_HERE, "..", "include", "tfgx_seggram.h")],
-                "tfgx_normgrad.hip": [os.path.join(_HERE, "..", "include", "tfgx_normgrad.h")],
-                "tfgx_collate.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h")],
-                "tfgx_collate_static.hip": [collate_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
-                                            os.path.join(_HERE, "..", "include", "tfgx_collate_static.h")],
-                "tfgx_pool_static.hip": [host_hdr, topk_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
-                                         os.path.join(_HERE, "..", "include", "tfgx_pool_static.h")],
-                "tfgx_rows3d.hip": [host_hdr, topk_hdr, os.path.join(_HERE, "..", "include", "tfgx_collate.h"),
-                                    os.path.join(_HERE, "..", "include", "tfgx_pool_static.h"),
-                                    os.path.join(_HERE, "..", "include", "tfgx_rows3d.h")]}
+    deps = _headers()
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
-        if force or _newer(s, o) or any(_newer(d, o) for d in deps) or any(_newer(d, o) for d in own_deps.get(src, [])):
+        if force or _newer(s, o) or any(_newer(d, o) for d in deps):
             jobs.append((s, o))
 
     def compile_one(job):
@@ -220,7 +186,6 @@ ASAN_LIB = os.path.join(ASAN_DIR, "libtfgx.so")
 
 def asan_runtime():
     """Path of clang's shared AddressSanitizer runtime (must be LD_PRELOADed into an uninstrumented host process)."""
-    import glob
     hits = sorted(glob.glob(os.path.join(ROCM, "lib", "llvm", "lib", "clang", "*", "lib", "linux",
                                          "libclang_rt.asan-x86_64.so")))
     return hits[-1] if hits else None
@@ -232,9 +197,7 @@ def build_asan(force=False, verbose=True):
     tests/test_abi.py::test_host_code_under_address_sanitizer and tools/asan_host_check.py."""
     os.makedirs(ASAN_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC, x) for x in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "tfgx_common.h"), os.path.join(CSRC, "tfgx_sample_rows.h"),
-                   os.path.join(CSRC, "tfgx_host.h"), os.path.join(CSRC, "tfgx_widen_h16.h"),
-                   os.path.join(_HERE, "..", "include", "tfgx.h")]
+    deps = srcs + _headers()
     if not force and os.path.exists(ASAN_LIB) and not any(_newer(d, ASAN_LIB) for d in deps):
         return ASAN_LIB
     flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",

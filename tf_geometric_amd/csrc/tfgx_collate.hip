@@ -41,19 +41,9 @@ extern "C" int tfgx_collate(const tfgx_collate_args* a, tfgx_stream_t stream_)
     TFGX_RANGE();
     hipStream_t stream = as_stream(stream_);
     TFGX_REQUIRE(a != nullptr, "args is null");
-    const struct { const char* name; int64_t v; } sizes[] = {{"ds_ldx", a->ds_ldx}, {"F", a->F}, {"ds_n", a->ds_n}, {"ds_e", a->ds_e},
-                                                             {"B", a->B}, {"n_out", a->n_out}, {"e_out", a->e_out},
-                                                             {"out_ldx", a->out_ldx}};
-    for (const auto& s : sizes) {
-        if (s.v < 0) {
-            set_error("tfgx_collate: negative size (%s = %lld)", s.name, (long long)s.v);
-            return TFGX_ERR_INVALID_ARG;
-        }
-        if (s.v >= kMaxSize) {
-            set_error("tfgx_collate: %s = %lld does not fit int32", s.name, (long long)s.v);
-            return TFGX_ERR_INVALID_ARG;
-        }
-    }
+    const NamedSize sizes[] = {{"ds_ldx", a->ds_ldx}, {"F", a->F}, {"ds_n", a->ds_n}, {"ds_e", a->ds_e}, {"B", a->B},
+                               {"n_out", a->n_out}, {"e_out", a->e_out}, {"out_ldx", a->out_ldx}};
+    if (int rc = check_sizes("tfgx_collate", sizes)) return rc;
     if (a->n_out > a->ds_n * a->B) {       // both factors are below 2^31: no overflow
         set_error("tfgx_collate: n_out = %lld is more than B = %lld graphs of a dataset of ds_n = %lld nodes can hold",
                   (long long)a->n_out, (long long)a->B, (long long)a->ds_n);

@@ -4,13 +4,15 @@
 //
 // Reference: tf_geometric/data/graph.py:463-560 (BatchGraph.from_graphs), demo/demo_mean_pool.py (a batch per step).
 //
-// table  : ONE workgroup of kScanBlock threads; thread t owns the contiguous slots [t, t + 1) * ceil(B / kScanBlock).  Two
-//          exclusive scans of (nodes, edges) pairs in int64: over the IN-RANGE slots, which decides who is live (both cumulated
-//          totals within the capacities), then over the LIVE slots, which gives the output offsets.  Wave scans with shuffles,
-//          the 16 wave totals through LDS.  The live count and the flags are integer LDS atomics (add / or: commutative).
+// table  : ONE workgroup of kScanBlock threads; thread t owns a contiguous run of slots (tfgx_compact.h: thread_run).  Two
+//          exclusive scans of (nodes, edges) pairs in int64 (tfgx_compact.h: block_exclusive_scan): over the IN-RANGE slots,
+//          which decides who is live (both cumulated totals within the capacities), then over the LIVE slots, which gives the
+//          output offsets.  The live count and the flags are integer LDS atomics (add / or: commutative).
 // collate: the sections of tfgx_collate_tiles.h at STATIC = true, and behind them a graph section that copies out_node_ptr into
 //          graph_row_ptr and closes it with n_cap.  No atomics.
 #include "tfgx_common.h"
+#include "tfgx_host.h"
+#include "tfgx_compact.h"
 #include "tfgx_collate_tiles.h"
 #include "../../include/tfgx_collate_static.h"
 
@@ -19,8 +21,7 @@ namespace {
 
 using namespace collate;
 
-constexpr int kScanBlock = 1024;
-constexpr int kScanWaves = kScanBlock / kWave;
+using compact::kScanBlock;
 static_assert(int64_t(TFGX_STATIC_BATCH_MAX_SLOTS) >= 65535, "the scan covers at least 65 535 slots");
 
 struct Pair {
@@ -28,45 +29,20 @@ struct Pair {
 };
 
 __device__ __forceinline__ Pair operator+(Pair a, Pair b) { return Pair{a.n + b.n, a.e + b.e}; }
-
-// exclusive prefix of `v` over the workgroup's threads; `total` = the sum over all of them.  Two barriers.
-__device__ __forceinline__ Pair block_exclusive_scan(Pair v, Pair* wave_total, Pair& total)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    Pair inc = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const long long n = __shfl_up(static_cast<long long>(inc.n), off, kWave);
-        const long long e = __shfl_up(static_cast<long long>(inc.e), off, kWave);
-        if (lane >= off) inc = inc + Pair{n, e};
-    }
-    if (lane == kWave - 1) wave_total[wave] = inc;
-    __syncthreads();
-    Pair base{0, 0};
-    total = Pair{0, 0};
-    for (int w = 0; w < kScanWaves; ++w) {
-        const Pair t = wave_total[w];
-        if (w < wave) base = base + t;
-        total = total + t;
-    }
-    __syncthreads();                                    // wave_total is free again
-    return Pair{base.n + inc.n - v.n, base.e + inc.e - v.e};
-}
+__device__ __forceinline__ Pair operator-(Pair a, Pair b) { return Pair{a.n - b.n, a.e - b.e}; }
+__device__ __forceinline__ Pair shfl_up(Pair v, int off) { return Pair{compact::shfl_up(v.n, off), compact::shfl_up(v.e, off)}; }
 
 __global__ void __launch_bounds__(kScanBlock) collate_static_table_kernel(
     const int32_t* __restrict__ ids, int32_t B, const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ edge_ptr,
     int32_t G, int64_t max_nodes, int64_t max_edges, int32_t* __restrict__ table, uint8_t* __restrict__ live_mask,
     int32_t* __restrict__ counts)
 {
-    __shared__ Pair wave_total[kScanWaves];
     __shared__ int32_t s_live, s_flags;
     if (threadIdx.x == 0) {
         s_live = 0;
         s_flags = 0;
     }
-    const int32_t per = (B + kScanBlock - 1) / kScanBlock;
-    const int32_t begin = int32_t(min(int64_t(B), int64_t(threadIdx.x) * per));
-    const int32_t end = int32_t(min(int64_t(B), int64_t(begin) + per));
+    const auto [begin, end] = compact::thread_run(B);
     // 1. the in-range slots: an id is compared before it is used as an index
     Pair mine{0, 0};
     int32_t flags = 0;
@@ -76,7 +52,7 @@ __global__ void __launch_bounds__(kScanBlock) collate_static_table_kernel(
         else if (id != TFGX_STATIC_BATCH_DEAD) flags |= TFGX_STATIC_BATCH_BAD_ID;
     }
     Pair total;
-    const Pair before = block_exclusive_scan(mine, wave_total, total);
+    const Pair before = compact::block_exclusive_scan(mine, total);
     // 2. who is live: both cumulated totals through the slot within the capacities
     Pair live{0, 0}, run = before;
     int32_t n_live_slots = 0;
@@ -92,7 +68,7 @@ __global__ void __launch_bounds__(kScanBlock) collate_static_table_kernel(
             flags |= TFGX_STATIC_BATCH_OVERFLOW;
         }
     }
-    const Pair out0 = block_exclusive_scan(live, wave_total, total);      // total: n_live, e_live (within the capacities: int32)
+    const Pair out0 = compact::block_exclusive_scan(live, total);      // total: n_live, e_live (within the capacities: int32)
     // 3. the table
     const int64_t stride = int64_t(B) + 1;
     Pair out = out0;
@@ -151,28 +127,6 @@ __global__ void __launch_bounds__(kBlock) collate_static_kernel(const Params p)
     else graph_tile(p, int32_t(b - p.x_tiles - p.node_tiles - p.edge_tiles));
 }
 
-struct NamedSize {
-    const char* name;
-    int64_t v;
-};
-
-// every size is non-negative and fits int32
-template <size_t N>
-int check_sizes(const char* entry, const NamedSize (&sizes)[N])
-{
-    for (const auto& s : sizes) {
-        if (s.v < 0) {
-            set_error("%s: negative size (%s = %lld)", entry, s.name, (long long)s.v);
-            return TFGX_ERR_INVALID_ARG;
-        }
-        if (s.v >= kMaxSize) {
-            set_error("%s: %s = %lld does not fit int32", entry, s.name, (long long)s.v);
-            return TFGX_ERR_INVALID_ARG;
-        }
-    }
-    return TFGX_OK;
-}
-
 }  // namespace
 }  // namespace tfgx
 
@@ -220,19 +174,9 @@ extern "C" int tfgx_static_batch(const tfgx_static_batch_args* a, tfgx_stream_t 
                                {"n_cap", a->n_cap}, {"e_cap", a->e_cap}, {"sinks", a->sinks}, {"sink_degree", a->sink_degree},
                                {"out_ldx", a->out_ldx}};
     if (int rc = check_sizes("tfgx_static_batch", sizes)) return rc;
-    if (a->sink_degree < 1) {
-        set_error("tfgx_static_batch: sink_degree = %lld must be at least 1", (long long)a->sink_degree);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (a->sinks > a->n_cap) {
-        set_error("tfgx_static_batch: sinks = %lld is more than n_cap = %lld rows", (long long)a->sinks, (long long)a->n_cap);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (a->sinks * a->sink_degree < a->e_cap) {        // both factors are below 2^31: no overflow
-        set_error("tfgx_static_batch: sinks = %lld of sink_degree = %lld cannot hold a tail of e_cap = %lld padded edges",
-                  (long long)a->sinks, (long long)a->sink_degree, (long long)a->e_cap);
-        return TFGX_ERR_INVALID_ARG;
-    }
+    if (int rc = check_sink_degree("tfgx_static_batch", a->sink_degree)) return rc;
+    if (int rc = check_sinks_within("tfgx_static_batch", a->sinks, "n_cap", a->n_cap)) return rc;
+    if (int rc = check_sink_tail("tfgx_static_batch", a->sinks, a->sink_degree, a->e_cap)) return rc;
     const bool has_x = a->n_cap > 0 && a->F > 0;
     if (has_x && a->ds_ldx < a->F) {
         set_error("tfgx_static_batch: ds_ldx = %lld is smaller than F = %lld", (long long)a->ds_ldx, (long long)a->F);

@@ -19,6 +19,7 @@
 //   follow every live row and do not decrease with q, so a stable sort leaves the tail where it is.
 #pragma once
 #include "tfgx_common.h"
+#include "tfgx_host.h"
 #include "../../include/tfgx_collate.h"
 
 namespace tfgx {
@@ -28,8 +29,6 @@ constexpr int kTile = TFGX_COLLATE_TILE;               // output elements per wo
 constexpr int kItems = kTile / kBlock;                 // 4 per thread: one float4 on the vector path
 constexpr int kLdsOffsets = 1024;                      // B + 1 <= this: the offsets are searched in LDS (4 KiB)
 static_assert(kTile == kBlock * 4, "the vector path moves one float4 per thread and tile");
-
-constexpr int64_t kMaxSize = (int64_t(1) << 31) - 1;
 
 struct PlanDev {
     const int32_t* ds_row_ptr;

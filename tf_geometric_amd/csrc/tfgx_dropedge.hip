@@ -6,7 +6,7 @@
 //   edge order : (row, col) of the kept edges + their ids              -> out_row / out_col / out_edge_id
 //   CSR order  : the parent plan's (col, perm), by destination          -> the dropped list's plan
 //   CSR order  : the parent's transposed plan, by source                -> the dropped list's transposed plan
-// Every compaction is the tile scheme of tfgx_subgraph.hip: tiles of kTile items, per-tile counts, one scan, then wave
+// Every compaction is the tile scheme of tfgx_compact.h: tiles of kTile items, per-tile counts, one scan, then wave
 // ballot + mbcnt inside the tile.  Each pass also leaves a GROUP TABLE: per 64 consecutive items {keep bits, kept items
 // before the group}, 16 bytes.  rank(i) = table[i / 64].before + popcount(bits below i) then answers
 //   new perm[q]    = rank_edge_order(old perm[p])      (the new id of a kept edge)
@@ -15,25 +15,18 @@
 // walked: a row of one edge and a hub of a million take the same path.  Integer atomicOr on the bad-index flag only.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_compact.h"
 #include "../../include/tfgx_dropedge.h"
 #include <hipcub/hipcub.hpp>
 
 namespace tfgx {
 namespace {
 
-constexpr int kTileItems = 8;                          // items per thread per tile
-constexpr int kTile = kBlock * kTileItems;             // 2048 items per workgroup
-constexpr int kWavesPerBlock = kBlock / kWave;
+using namespace compact;
 
 enum { kEdges = 0, kUpperEdges = 1, kCsr = 2 };
 
-inline int64_t num_tiles(int64_t E) { return (E + kTile - 1) / kTile; }
 inline int64_t num_groups(int64_t E) { return (E + kWave - 1) / kWave; }
-
-__device__ __forceinline__ int lane_prefix(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
-}
 
 // tfgx_dropout_keep on the device: thr == 0 is "dropout off" (make_drop)
 __device__ __forceinline__ bool keep_id(uint32_t thr, uint64_t seed, uint32_t id)
@@ -74,25 +67,12 @@ __global__ void __launch_bounds__(kBlock) tile_count(const int32_t* __restrict__
                                                      int64_t n_a, int64_t n_b, uint32_t thr, uint64_t seed,
                                                      int32_t* __restrict__ tile_cnt, int32_t* __restrict__ flag)
 {
-    __shared__ int32_t wave_cnt[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t base = int64_t(blockIdx.x) * kTile;
-    int cnt = 0, bad = 0;
-#pragma unroll
-    for (int it = 0; it < kTileItems; ++it)
-        cnt += __popcll(__ballot(item_keep<MODE>(a, b, base + it * kBlock + threadIdx.x, E, n_a, n_b, thr, seed, bad)));
-    if (MODE != kCsr && __any(bad) && lane == 0) atomicOr(flag, 1);
-    if (lane == 0) wave_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) t += wave_cnt[w];
-        tile_cnt[blockIdx.x] = t;
-    }
+    int bad = 0;
+    compact::tile_count([&](int64_t i) { return item_keep<MODE>(a, b, i, E, n_a, n_b, thr, seed, bad); }, tile_cnt);
+    if (MODE != kCsr && __any(bad) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(flag, 1);
 }
 
-// Order-stable compaction: item i = base + it * kBlock + wave * 64 + lane lands at
-// tile_off[tile] + (kept items of earlier (it, wave) slots of the tile) + (kept lanes below it in its wave).
+// The order-stable compaction of tfgx_compact.h:
 //   kEdges      : out_a / out_b / out_c [pos] = row, col, edge id
 //   kUpperEdges : the same, and the flipped edge with the same id at [half + pos]
 //   kCsr        : out_a [pos] = col (b), out_b [pos] = new id of edge perm (a) through the edge-order group table `rank_of`
@@ -104,15 +84,13 @@ __global__ void __launch_bounds__(kBlock) tile_emit(const int32_t* __restrict__ 
                                                     int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
                                                     int32_t* __restrict__ out_c, int4* __restrict__ table)
 {
-    __shared__ int32_t slot_cnt[kTileItems][kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t base = int64_t(blockIdx.x) * kTile;
+    const int lane = threadIdx.x & (kWave - 1);
     uint64_t mask[kTileItems];
     int32_t va[kTileItems], vb[kTileItems];
     int unused = 0;
 #pragma unroll
     for (int it = 0; it < kTileItems; ++it) {
-        const int64_t i = base + it * kBlock + threadIdx.x;
+        const int64_t i = tile_item(it);
         va[it] = 0;
         vb[it] = 0;
         if (i < E) {
@@ -121,22 +99,11 @@ __global__ void __launch_bounds__(kBlock) tile_emit(const int32_t* __restrict__ 
         }
         // the count pass validated the endpoints; n_a = n_b = INT32_MAX: no range to check here
         mask[it] = __ballot(item_keep<MODE>(a, b, i, E, int64_t(1) << 31, int64_t(1) << 31, thr, seed, unused));
-        if (lane == 0) slot_cnt[it][wave] = __popcll(mask[it]);
     }
-    __syncthreads();
-    int32_t off = tile_off[blockIdx.x];
-#pragma unroll
-    for (int it = 0; it < kTileItems; ++it) {
-        int32_t before = 0, total = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) {
-            const int32_t c = slot_cnt[it][w];
-            before += (w < wave) ? c : 0;
-            total += c;
-        }
-        const int64_t i = base + it * kBlock + threadIdx.x;
+    compact::tile_positions(mask, tile_off, [&](int it, int32_t first, int32_t pos) {
+        const int64_t i = tile_item(it);
         if (table != nullptr && lane == 0 && i < E)
-            table[i >> 6] = make_int4(int32_t(uint32_t(mask[it])), int32_t(uint32_t(mask[it] >> 32)), off + before, 0);
-        const int32_t pos = off + before + lane_prefix(mask[it]);
+            table[i >> 6] = make_int4(int32_t(uint32_t(mask[it])), int32_t(uint32_t(mask[it] >> 32)), first, 0);
         if (((mask[it] >> lane) & 1) && pos < cap) {
             if constexpr (MODE == kCsr) {
                 out_a[pos] = vb[it];
@@ -152,8 +119,7 @@ __global__ void __launch_bounds__(kBlock) tile_emit(const int32_t* __restrict__ 
                 }
             }
         }
-        off += total;
-    }
+    });
 }
 
 // out_row_ptr[r] = kept CSR positions below parent_row_ptr[r]; `total` (device) = all kept positions
@@ -184,11 +150,7 @@ Layout layout(int64_t E, int with_any_plan)
     Layout L;
     L.nt = num_tiles(E);
     L.ng = num_groups(E);
-    size_t scan = 0;
-    const int32_t* in = nullptr;
-    int32_t* out = nullptr;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, in, out, static_cast<int>(L.nt + 1));
-    L.temp_bytes = align256(scan);
+    L.temp_bytes = align256(scan_bytes(L.nt + 1));
     const size_t tiles = align256(sizeof(int32_t) * size_t(L.nt + 2));
     const size_t table = with_any_plan ? align256(sizeof(int4) * size_t(L.ng > 0 ? L.ng : 1)) : 0;
     L.off_tile_cnt = 0;

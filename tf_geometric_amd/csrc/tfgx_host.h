@@ -21,6 +21,44 @@ inline int check_size(const char* fn, const char* name, int64_t v)
     return TFGX_OK;
 }
 
+struct NamedSize {
+    const char* name;
+    int64_t v;
+};
+
+// check_size over a list; the first size that is refused decides the message
+template <size_t N>
+int check_sizes(const char* fn, const NamedSize (&sizes)[N])
+{
+    for (const auto& s : sizes)
+        if (int rc = check_size(fn, s.name, s.v)) return rc;
+    return TFGX_OK;
+}
+
+// The refusals of a padded tail (fixed-shape batches: the last `sinks` rows hold the e_cap padded edges, sink_degree to a row).
+// One helper per refusal: every entry point calls them in its own order, and the first that fires decides the message.
+inline int check_sink_degree(const char* fn, int64_t sink_degree)
+{
+    if (sink_degree >= 1) return TFGX_OK;
+    set_error("%s: sink_degree = %lld must be at least 1", fn, (long long)sink_degree);
+    return TFGX_ERR_INVALID_ARG;
+}
+
+inline int check_sinks_within(const char* fn, int64_t sinks, const char* rows_name, int64_t rows)
+{
+    if (sinks <= rows) return TFGX_OK;
+    set_error("%s: sinks = %lld is more than %s = %lld rows", fn, (long long)sinks, rows_name, (long long)rows);
+    return TFGX_ERR_INVALID_ARG;
+}
+
+inline int check_sink_tail(const char* fn, int64_t sinks, int64_t sink_degree, int64_t e_cap)
+{
+    if (sinks * sink_degree >= e_cap) return TFGX_OK;      // both factors are below 2^31: no overflow
+    set_error("%s: sinks = %lld of sink_degree = %lld cannot hold a tail of e_cap = %lld padded edges", fn, (long long)sinks,
+              (long long)sink_degree, (long long)e_cap);
+    return TFGX_ERR_INVALID_ARG;
+}
+
 inline int null_arg(const char* fn, const char* name)
 {
     set_error("%s: %s is null", fn, name);

@@ -18,6 +18,7 @@
 // tfgx_samplereduce.hip.  The gather out of a 16-bit table (include/tfgx_minibatch_h16.h) sits next to the float32 one.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_gather.h"
 #include "tfgx_sample_rows.h"
 #include "tfgx_widen_h16.h"
 #include "../../include/tfgx_nbrblock.h"
@@ -117,14 +118,6 @@ __global__ void iota_kernel(int64_t n, int32_t* __restrict__ out)
     int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
     const int64_t stride = int64_t(gridDim.x) * blockDim.x;
     for (; i < n; i += stride) out[i] = int32_t(i);
-}
-
-__global__ void gather_by_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int64_t n,
-                                 int32_t* __restrict__ dst)
-{
-    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[idx[i]];
 }
 
 // keys sorted ascending, every key in [0, n): row_ptr[v] = the first position whose key is >= v (tfgx_plan.hip's rule)
@@ -356,8 +349,8 @@ extern "C" int tfgx_nbrstatic_transpose(const int32_t* block_row, const int32_t*
     // a stable LSD radix sort of (source, position): equal sources keep their block order
     TFGX_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, block_col, keys_out, iota, t_perm, static_cast<int>(E), 0,
                                                       key_bits(n), stream));
-    gather_by_kernel<<<grid, kBlock, 0, stream>>>(block_row, t_perm, E, t_col);
-    TFGX_LAUNCH_CHECK("gather_by_kernel");
+    gather_by_index<<<grid, kBlock, 0, stream>>>(block_row, t_perm, E, t_col);
+    TFGX_LAUNCH_CHECK("gather_by_index");
     row_ptr_of_sorted_kernel<<<grid_for(E + 1, kBlock), kBlock, 0, stream>>>(keys_out, E, int32_t(n), t_row_ptr);
     TFGX_LAUNCH_CHECK("row_ptr_of_sorted_kernel");
     return TFGX_OK;

@@ -6,6 +6,7 @@
 // then row_ptr from the sorted keys' boundaries (no atomics, no scan).
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_gather.h"
 #include <hipcub/hipcub.hpp>
 #include <dlfcn.h>
 #include <cstdlib>
@@ -86,14 +87,6 @@ __global__ void row_ptr_from_sorted(const int32_t* __restrict__ keys, int64_t E,
         const int32_t hi = (i == E) ? n_dst : keys[i];
         for (int32_t k = lo; k <= hi; ++k) row_ptr[k] = static_cast<int32_t>(i);
     }
-}
-
-__global__ void gather_i32(const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int64_t n,
-                           int32_t* __restrict__ dst)
-{
-    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[idx[i]];
 }
 
 __global__ void permute_rows(const float* __restrict__ src, const int32_t* __restrict__ perm, int64_t E,
@@ -224,8 +217,8 @@ extern "C" int tfgx_build_csr_by_dst(const int32_t* row, const int32_t* col, int
     }
     TFGX_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, row, keys_out, iota, perm,
                                                       static_cast<int>(E), 0, key_bits(n_dst), stream));
-    gather_i32<<<grid_for(E, kBlock), kBlock, 0, stream>>>(col, perm, E, col_sorted);
-    TFGX_LAUNCH_CHECK("gather_i32");
+    gather_by_index<<<grid_for(E, kBlock), kBlock, 0, stream>>>(col, perm, E, col_sorted);
+    TFGX_LAUNCH_CHECK("gather_by_index");
     row_ptr_from_sorted<<<grid_for(E + 1, kBlock), kBlock, 0, stream>>>(keys_out, E, int32_t(n_dst), row_ptr);
     TFGX_LAUNCH_CHECK("row_ptr_from_sorted");
     return TFGX_OK;

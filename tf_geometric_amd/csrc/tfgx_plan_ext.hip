@@ -9,12 +9,13 @@
 //   order slot    : one binary search per hub row.
 //   source blocks : ONE wave per destination row, no sort, no workspace: pass 1 counts the row's edges per block (lane b
 //                   owns block b's counter), a wave scan turns the counts into rpk, pass 2 writes col_k in place with the
-//                   same order-stable ballot compaction as tfgx_subgraph.hip (per distinct block in a 64-edge chunk: one
+//                   ballot + lane_prefix of tfgx_compact.h, order-stable (per distinct block in a 64-edge chunk: one
 //                   ballot, one readlane of the block's cursor).  col is read twice (the second read mostly from cache),
 //                   col_k written once, rpk once.
 // Integer atomics only (the degree maximum); never on floats.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_compact.h"
 #include <hipcub/hipcub.hpp>
 #include <cmath>
 
@@ -147,11 +148,6 @@ __global__ void hub_order_slot_kernel(const int32_t* __restrict__ hub_rows, int6
 }
 
 // ---- source blocks ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int lane_below(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
-}
-
 // One wave per destination row r.  Lane b (< KB) keeps block b's edge counter (pass 1), then its cursor (pass 2).
 // An edge's block is clamped to [0, KB): whatever col holds, every write stays inside the row's own positions.
 __global__ void __launch_bounds__(kBlock) source_blocks_kernel(const int32_t* __restrict__ row_ptr,
@@ -203,7 +199,7 @@ __global__ void __launch_bounds__(kBlock) source_blocks_kernel(const int32_t* __
                 const uint64_t m = pending & __ballot(bb == b);
                 const int32_t at = __builtin_amdgcn_readlane(cursor, b);
                 if ((m >> lane) & 1) {
-                    const int64_t pos = int64_t(at) + lane_below(m & below);
+                    const int64_t pos = int64_t(at) + compact::lane_prefix(m & below);
                     if (pos >= 0 && pos < E) col_k[pos] = c;
                 }
                 if (lane == b) cursor += __popcll(m);

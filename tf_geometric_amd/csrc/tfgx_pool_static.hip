@@ -4,7 +4,8 @@
 //
 // Reference: tf_geometric/nn/pool/topk_pool.py:6-87, nn/pool/sag_pool.py:7-45, data/graph.py:276-359.
 //
-// table  : ONE workgroup of kScanBlock threads, thread t owns a contiguous run of slots; an exclusive scan of k_g.
+// table  : ONE workgroup of kScanBlock threads, thread t owns a contiguous run of slots; an exclusive scan of k_g (the scan and
+//          the runs are tfgx_compact.h's, and so is the tile compaction of the edges below).
 // select : one workgroup per slot.  The slot's (descending_bits(score) << 32 | position) keys go to LDS; every node's rank is the
 //          number of keys below its own — the keys are distinct, so the ranks are a permutation, ties fall in row order, and
 //          the order is that of tfgx_segment_topk's stable radix sort on the same 32 bits.  Each thread holds kSelItems keys in
@@ -17,53 +18,24 @@
 // No global atomics, no float atomics: every output is a pure function of the inputs.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_compact.h"
+#include "tfgx_gather.h"
+#include "tfgx_collate_tiles.h"
 #include "tfgx_topk_keys.h"
 #include "../../include/tfgx_pool_static.h"
 
 namespace tfgx {
 namespace {
 
-constexpr int kScanBlock = 1024;
-constexpr int kScanWaves = kScanBlock / kWave;
+using namespace compact;
+using collate::PlanDev;
+
 constexpr int kMaxGraph = TFGX_STATIC_POOL_MAX_GRAPH_NODES;
 constexpr int kSelItems = 4;                           // keys a thread ranks per pass over the LDS keys
 constexpr int kFillTile = kBlock * 4;                  // rows per workgroup of the fill sections
-constexpr int kTileItems = 8;                          // edges per thread per tile
-constexpr int kTile = kBlock * kTileItems;             // 2048 edges per workgroup
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kRowLanes = 8;                           // lanes that walk one pooled row (graph batches: a few edges per node)
 constexpr int kRowsPerBlock = kBlock / kRowLanes;
 static_assert(kMaxGraph % (kBlock * kSelItems) == 0, "the cap is a whole number of ranking passes");
-
-__device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return max(lo, min(v, hi)); }
-
-__device__ __forceinline__ int lane_prefix(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
-}
-
-// exclusive prefix of `v` over the kScanBlock threads; `total` = the sum over all of them.  Two barriers.
-__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t* wave_total, int64_t& total)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const long long up = __shfl_up(static_cast<long long>(inc), off, kWave);
-        if (lane >= off) inc += up;
-    }
-    if (lane == kWave - 1) wave_total[wave] = inc;
-    __syncthreads();
-    int64_t base = 0;
-    total = 0;
-    for (int w = 0; w < kScanWaves; ++w) {
-        const int64_t t = wave_total[w];
-        if (w < wave) base += t;
-        total += t;
-    }
-    __syncthreads();                                    // wave_total is free again
-    return base + inc - v;
-}
 
 // ---- (a) the pooled table ----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t kept_of_slot(const int32_t* __restrict__ grp, int32_t j, int32_t k, float ratio, int32_t& flags)
@@ -80,17 +52,14 @@ __global__ void __launch_bounds__(kScanBlock) pool_table_kernel(const int32_t* _
                                                                 int32_t B, int32_t k, float ratio, int32_t m_max, int32_t n_cap_out,
                                                                 int32_t* __restrict__ prp, int32_t* __restrict__ counts)
 {
-    __shared__ int64_t wave_total[kScanWaves];
     __shared__ int32_t s_flags;
     if (threadIdx.x == 0) s_flags = 0;
-    const int32_t per = (B + kScanBlock - 1) / kScanBlock;
-    const int32_t begin = int32_t(min(int64_t(B), int64_t(threadIdx.x) * per));
-    const int32_t end = int32_t(min(int64_t(B), int64_t(begin) + per));
+    const auto [begin, end] = thread_run(B);
     int64_t mine = 0;
     int32_t flags = 0;
     for (int32_t j = begin; j < end; ++j) mine += kept_of_slot(grp, j, k, ratio, flags);
     int64_t total;
-    int64_t run = block_exclusive_scan(mine, wave_total, total);
+    int64_t run = block_exclusive_scan(mine, total);
     for (int32_t j = begin; j < end; ++j) {
         prp[j] = int32_t(min(run, int64_t(m_max)));
         run += kept_of_slot(grp, j, k, ratio, flags);
@@ -176,15 +145,6 @@ __global__ void __launch_bounds__(kBlock) pool_select_kernel(const float* __rest
 }
 
 // ---- (c) pooled edges and plans ------------------------------------------------------------------------------------------------
-struct PlanDev {
-    const int32_t* p_row_ptr;
-    const int32_t* p_col;
-    const int32_t* p_perm;
-    int32_t* row_ptr;
-    int32_t* col;
-    int32_t* perm;
-};
-
 struct EdgeParams {
     const int32_t* row;
     const int32_t* col;
@@ -201,7 +161,7 @@ struct EdgeParams {
     int32_t* out_edge_id;
     int32_t* out_egi;
     float* out_w;
-    PlanDev plan[2];
+    PlanDev plan[2];                   // ds_* = the parent's plan, out_* = the pooled one
     int32_t* counts;
     int32_t* tile_cnt;                 // [nt]
     int32_t* tile_off;                 // [nt + 1]
@@ -230,13 +190,13 @@ __device__ __forceinline__ void parent_span(const EdgeParams& p, int k, int32_t 
     if (j >= m_live) return;
     const int32_t o = p.node_index[j];
     if (o < 0 || o >= p.n_cap) return;
-    s = clampi(p.plan[k].p_row_ptr[o], 0, p.e_cap);
-    t = clampi(p.plan[k].p_row_ptr[o + 1], s, p.e_cap);
+    s = clampi(p.plan[k].ds_row_ptr[o], 0, p.e_cap);
+    t = clampi(p.plan[k].ds_row_ptr[o + 1], s, p.e_cap);
 }
 
 __device__ __forceinline__ int32_t mapped_source(const EdgeParams& p, int k, int32_t pos)
 {
-    const int32_t c = p.plan[k].p_col[pos];
+    const int32_t c = p.plan[k].ds_col[pos];
     if (c < 0 || c >= p.n_cap) return -1;
     const int32_t nc = p.node_map[c];
     return nc < p.m_rows ? nc : -1;
@@ -245,27 +205,17 @@ __device__ __forceinline__ int32_t mapped_source(const EdgeParams& p, int k, int
 // sections: [0, nt) kept edges per tile; behind them kept edges per pooled row, kRowLanes lanes to a row, both plans
 __global__ void __launch_bounds__(kBlock) pool_count_kernel(const EdgeParams p)
 {
-    __shared__ int32_t wave_cnt[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     if (int32_t(blockIdx.x) < p.nt) {
-        const int64_t base = int64_t(blockIdx.x) * kTile;
-        int cnt = 0;
-#pragma unroll
-        for (int it = 0; it < kTileItems; ++it) {
-            int32_t nr, nc;
-            cnt += __popcll(__ballot(kept_edge(p, base + it * kBlock + threadIdx.x, nr, nc)));
-        }
-        if (lane == 0) wave_cnt[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t = 0;
-            for (int w = 0; w < kWavesPerBlock; ++w) t += wave_cnt[w];
-            p.tile_cnt[blockIdx.x] = t;
-        }
+        tile_count(
+            [&](int64_t e) {
+                int32_t nr, nc;
+                return kept_edge(p, e, nr, nc);
+            },
+            p.tile_cnt);
         return;
     }
     const int32_t m_live = live_pooled_rows(p);
-    const int lig = lane % kRowLanes, shift = lane - lig;
+    const int lig = threadIdx.x % kRowLanes;
     const int64_t j64 = (int64_t(blockIdx.x) - p.nt) * kRowsPerBlock + threadIdx.x / kRowLanes;
     if (j64 >= p.m_rows) return;
     const int32_t j = int32_t(j64);
@@ -274,8 +224,7 @@ __global__ void __launch_bounds__(kBlock) pool_count_kernel(const EdgeParams p)
         parent_span(p, k, j, m_live, s, t);
         for (int32_t b = s; b < t; b += kRowLanes) {
             const int32_t pos = b + lig;
-            const bool keep = pos < t && mapped_source(p, k, pos) >= 0;
-            c += __popcll((__ballot(keep) >> shift) & ((uint64_t(1) << kRowLanes) - 1));
+            c += __popcll(group_bits<kRowLanes>(pos < t && mapped_source(p, k, pos) >= 0));
         }
         if (lig == 0) p.row_cnt[int64_t(k) * p.m_rows + j] = c;
     }
@@ -285,18 +234,15 @@ __global__ void __launch_bounds__(kBlock) pool_count_kernel(const EdgeParams p)
 // exclusive sums of row_cnt over the rows that can be live (a dead one counts 0), then the sink rows in closed form.
 __global__ void __launch_bounds__(kScanBlock) pool_scan_kernel(const EdgeParams p)
 {
-    __shared__ int64_t wave_total[kScanWaves];
     const bool tiles = blockIdx.x == 0;
     const int32_t n = tiles ? p.nt : p.m_rows;
     const int32_t* in = tiles ? p.tile_cnt : p.row_cnt + int64_t(blockIdx.x - 1) * p.m_rows;
-    int32_t* out = tiles ? p.tile_off : p.plan[blockIdx.x - 1].row_ptr;
-    const int32_t per = (n + kScanBlock - 1) / kScanBlock;
-    const int32_t begin = int32_t(min(int64_t(n), int64_t(threadIdx.x) * per));
-    const int32_t end = int32_t(min(int64_t(n), int64_t(begin) + per));
+    int32_t* out = tiles ? p.tile_off : p.plan[blockIdx.x - 1].out_row_ptr;
+    const auto [begin, end] = thread_run(n);
     int64_t mine = 0;
     for (int32_t j = begin; j < end; ++j) mine += in[j];
     int64_t total;
-    int64_t run = block_exclusive_scan(mine, wave_total, total);
+    int64_t run = block_exclusive_scan(mine, total);
     for (int32_t j = begin; j < end; ++j) {
         out[j] = int32_t(min(run, int64_t(p.e_cap)));
         run += in[j];
@@ -314,51 +260,33 @@ __global__ void __launch_bounds__(kScanBlock) pool_scan_kernel(const EdgeParams 
         out[p.m_rows + t] = e_kept + int32_t(min(int64_t(p.e_cap - e_kept), int64_t(t) * p.sink_degree));
 }
 
-// Order-stable compaction of tile blockIdx.x of the parent edges (edge e = base + it * kBlock + wave * 64 + lane lands at
-// tile_off[tile] + kept edges of earlier (it, wave) slots + kept lanes below it), then the part of the padded tail that lies in
-// output positions [base, base + kTile).
+// The order-stable compaction of tfgx_compact.h over tile blockIdx.x of the parent edges, then the part of the padded tail that
+// lies in the output positions of the same numbers, [blockIdx.x, blockIdx.x + 1) * kTile.
 __global__ void __launch_bounds__(kBlock) pool_emit_edges_kernel(const EdgeParams p)
 {
-    __shared__ int32_t slot_cnt[kTileItems][kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t base = int64_t(blockIdx.x) * kTile;
     const int32_t e_kept = clampi(p.tile_off[p.nt], 0, p.e_cap);
     uint64_t mask[kTileItems];
     int32_t nr[kTileItems], nc[kTileItems];
     bool keep[kTileItems];
 #pragma unroll
     for (int it = 0; it < kTileItems; ++it) {
-        keep[it] = kept_edge(p, base + it * kBlock + threadIdx.x, nr[it], nc[it]);
+        keep[it] = kept_edge(p, tile_item(it), nr[it], nc[it]);
         mask[it] = __ballot(keep[it]);
-        if (lane == 0) slot_cnt[it][wave] = __popcll(mask[it]);
     }
-    __syncthreads();
-    int32_t off = p.tile_off[blockIdx.x];
+    tile_positions(mask, p.tile_off, [&](int it, int32_t, int32_t pos) {
+        if (keep[it] && pos >= 0 && pos < e_kept) {
+            const int64_t e = tile_item(it);
+            p.out_row[pos] = nr[it];
+            p.out_col[pos] = nc[it];
+            p.out_edge_id[pos] = int32_t(e);
+            p.out_egi[pos] = p.egi[e];
+            if (p.out_w != nullptr) p.out_w[pos] = p.w != nullptr ? p.w[e] : 1.0f;
+            p.rank[e] = pos;
+        }
+    });
 #pragma unroll
     for (int it = 0; it < kTileItems; ++it) {
-        int32_t before = 0, total = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) {
-            const int32_t c = slot_cnt[it][w];
-            before += (w < wave) ? c : 0;
-            total += c;
-        }
-        if (keep[it]) {
-            const int64_t e = base + it * kBlock + threadIdx.x;
-            const int32_t pos = off + before + lane_prefix(mask[it]);
-            if (pos >= 0 && pos < e_kept) {
-                p.out_row[pos] = nr[it];
-                p.out_col[pos] = nc[it];
-                p.out_edge_id[pos] = int32_t(e);
-                p.out_egi[pos] = p.egi[e];
-                if (p.out_w != nullptr) p.out_w[pos] = p.w != nullptr ? p.w[e] : 1.0f;
-                p.rank[e] = pos;
-            }
-        }
-        off += total;
-    }
-#pragma unroll
-    for (int it = 0; it < kTileItems; ++it) {
-        const int64_t q64 = base + it * kBlock + threadIdx.x;
+        const int64_t q64 = tile_item(it);
         if (q64 < e_kept || q64 >= p.e_cap) continue;
         const int32_t q = int32_t(q64);
         const int32_t v = p.m_rows + (q - e_kept) / p.sink_degree;      // < n_cap_out: sinks * sink_degree >= e_cap
@@ -368,8 +296,8 @@ __global__ void __launch_bounds__(kBlock) pool_emit_edges_kernel(const EdgeParam
         p.out_egi[q] = p.B;
         if (p.out_w != nullptr) p.out_w[q] = 1.0f;
         for (int k = 0; k < 2; ++k) {                                   // its own CSR position in both plans
-            p.plan[k].col[q] = v;
-            p.plan[k].perm[q] = q;
+            p.plan[k].out_col[q] = v;
+            p.plan[k].out_perm[q] = q;
         }
     }
 }
@@ -379,8 +307,7 @@ __global__ void __launch_bounds__(kBlock) pool_emit_plans_kernel(const EdgeParam
 {
     const int32_t m_live = live_pooled_rows(p);
     const int32_t e_kept = clampi(p.tile_off[p.nt], 0, p.e_cap);
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lig = lane % kRowLanes, shift = lane - lig;
+    const int lig = threadIdx.x % kRowLanes;
     const uint64_t below = (uint64_t(1) << lig) - 1;
     const int64_t j64 = int64_t(blockIdx.x) * kRowsPerBlock + threadIdx.x / kRowLanes;
     if (j64 >= m_live) return;
@@ -388,17 +315,17 @@ __global__ void __launch_bounds__(kBlock) pool_emit_plans_kernel(const EdgeParam
     for (int k = 0; k < 2; ++k) {
         int32_t s, t;
         parent_span(p, k, j, m_live, s, t);
-        int32_t pos = p.plan[k].row_ptr[j];
+        int32_t pos = p.plan[k].out_row_ptr[j];
         for (int32_t b = s; b < t; b += kRowLanes) {
             const int32_t at = b + lig;
             const int32_t nc = at < t ? mapped_source(p, k, at) : -1;
-            const uint64_t bits = (__ballot(nc >= 0) >> shift) & ((uint64_t(1) << kRowLanes) - 1);
+            const uint64_t bits = group_bits<kRowLanes>(nc >= 0);
             if (nc >= 0) {
                 const int32_t q = pos + __popcll(bits & below);
-                const int32_t pe = p.plan[k].p_perm[at];
+                const int32_t pe = p.plan[k].ds_perm[at];
                 if (q >= 0 && q < e_kept) {
-                    p.plan[k].col[q] = nc;
-                    p.plan[k].perm[q] = (pe >= 0 && pe < p.e_cap) ? p.rank[pe] : -1;
+                    p.plan[k].out_col[q] = nc;
+                    p.plan[k].out_perm[q] = (pe >= 0 && pe < p.e_cap) ? p.rank[pe] : -1;
                 }
             }
             pos += __popcll(bits);
@@ -406,73 +333,10 @@ __global__ void __launch_bounds__(kBlock) pool_emit_plans_kernel(const EdgeParam
     }
 }
 
-// ---- (d) pooled features -----------------------------------------------------------------------------------------------------
-// out[i, :] = idx[i] >= 0 ? x[idx[i], :] * s[idx[i]] : 0.  The load is CLAMPED (row max(idx, 0), below n), the zero is a select.
-__global__ void pool_gather_scale_rows(const float* __restrict__ x, int64_t ldx, int64_t n, const int32_t* __restrict__ idx,
-                                       const float* __restrict__ s, int64_t M, int64_t F, int64_t F4, float* __restrict__ out,
-                                       int64_t ldo)
-{
-    const int64_t W = F4 + (F - 4 * F4);
-    const int64_t total = M * W;
-    int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; t < total; t += stride) {
-        const int64_t i = t / W, q = t - i * W;
-        const int32_t raw = idx[i];
-        const bool live = raw >= 0 && raw < n;
-        const int64_t r = min(int64_t(max(raw, 0)), n - 1);
-        const float sc = s != nullptr ? s[r] : 1.0f;
-        if (q < F4) {
-            float v[4];
-            load_vec<4>(x + r * ldx + 4 * q, v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = live ? v[k] * sc : 0.0f;
-            store_vec<4>(out + i * ldo + 4 * q, v);
-        } else {
-            const int64_t c = 4 * F4 + (q - F4);
-            const float v = x[r * ldx + c] * sc;
-            out[i * ldo + c] = live ? v : 0.0f;
-        }
-    }
-}
-
-struct NamedSize {
-    const char* name;
-    int64_t v;
-};
-
-template <size_t N>
-int check_sizes(const char* entry, const NamedSize (&sizes)[N])
-{
-    for (const auto& s : sizes)
-        if (int rc = check_size(entry, s.name, s.v)) return rc;
-    return TFGX_OK;
-}
-
 Workspace<4> edges_workspace(int64_t n_cap_out, int64_t e_cap)
 {
     const size_t nt = size_t((e_cap + kTile - 1) / kTile);
     return Workspace<4>{{4 * (nt + 1), 4 * (nt + 1), 8 * size_t(n_cap_out + 1), 4 * size_t(e_cap > 0 ? e_cap : 1)}};
-}
-
-int check_pool_plan(const char* entry, const char* which, const tfgx_collate_plan* pl, int64_t e_cap)
-{
-    if (pl == nullptr) {
-        set_error("%s: %s is null", entry, which);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    const char* bad = nullptr;
-    if (pl->ds_row_ptr == nullptr) bad = "ds_row_ptr";
-    else if (pl->out_row_ptr == nullptr) bad = "out_row_ptr";
-    else if (e_cap > 0 && pl->ds_col == nullptr) bad = "ds_col";
-    else if (e_cap > 0 && pl->ds_perm == nullptr) bad = "ds_perm";
-    else if (e_cap > 0 && pl->out_col == nullptr) bad = "out_col";
-    else if (e_cap > 0 && pl->out_perm == nullptr) bad = "out_perm";
-    if (bad != nullptr) {
-        set_error("%s: %s->%s is null", entry, which, bad);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    return TFGX_OK;
 }
 
 }  // namespace
@@ -525,10 +389,7 @@ extern "C" int tfgx_static_pool_select(const float* score, const int32_t* graph_
         set_error("%s: B = %lld is more than the %d slots of a pooled table", fn, (long long)B, TFGX_STATIC_POOL_MAX_SLOTS);
         return TFGX_ERR_INVALID_ARG;
     }
-    if (sinks > n_cap) {
-        set_error("%s: sinks = %lld is more than n_cap = %lld rows", fn, (long long)sinks, (long long)n_cap);
-        return TFGX_ERR_INVALID_ARG;
-    }
+    if (int rc = check_sinks_within(fn, sinks, "n_cap", n_cap)) return rc;
     if (n_cap == 0 && n_cap_out == 0) return TFGX_OK;
     if (graph_row_ptr == nullptr) return null_arg(fn, "graph_row_ptr");
     if (pooled_row_ptr == nullptr) return null_arg(fn, "pooled_row_ptr");
@@ -560,27 +421,18 @@ extern "C" int tfgx_static_pool_edges(const tfgx_static_pool_args* a, tfgx_strea
     const NamedSize sizes[] = {{"n_cap", a->n_cap}, {"e_cap", a->e_cap}, {"B", a->B}, {"sinks", a->sinks},
                                {"sink_degree", a->sink_degree}, {"n_cap_out", a->n_cap_out}};
     if (int rc = check_sizes(fn, sizes)) return rc;
-    if (a->sink_degree < 1) {
-        set_error("%s: sink_degree = %lld must be at least 1", fn, (long long)a->sink_degree);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (a->sinks > a->n_cap_out) {
-        set_error("%s: sinks = %lld is more than n_cap_out = %lld rows", fn, (long long)a->sinks, (long long)a->n_cap_out);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (a->sinks > a->n_cap) {
-        set_error("%s: sinks = %lld is more than n_cap = %lld rows", fn, (long long)a->sinks, (long long)a->n_cap);
-        return TFGX_ERR_INVALID_ARG;
-    }
-    if (a->sinks * a->sink_degree < a->e_cap) {        // both factors are below 2^31: no overflow
-        set_error("%s: sinks = %lld of sink_degree = %lld cannot hold a tail of e_cap = %lld padded edges", fn, (long long)a->sinks,
-                  (long long)a->sink_degree, (long long)a->e_cap);
-        return TFGX_ERR_INVALID_ARG;
-    }
+    if (int rc = check_sink_degree(fn, a->sink_degree)) return rc;
+    if (int rc = check_sinks_within(fn, a->sinks, "n_cap_out", a->n_cap_out)) return rc;
+    if (int rc = check_sinks_within(fn, a->sinks, "n_cap", a->n_cap)) return rc;
+    if (int rc = check_sink_tail(fn, a->sinks, a->sink_degree, a->e_cap)) return rc;
     // no rows and no edges, and nowhere to put the offsets of an empty batch: nothing exists to be written
     if (a->n_cap_out == 0 && a->e_cap == 0 && a->plan == nullptr && a->plan_t == nullptr && a->counts == nullptr) return TFGX_OK;
-    if (int rc = check_pool_plan(fn, "plan", a->plan, a->e_cap)) return rc;
-    if (int rc = check_pool_plan(fn, "plan_t", a->plan_t, a->e_cap)) return rc;
+    const tfgx_collate_plan* plans[2] = {a->plan, a->plan_t};
+    const char* const which[2] = {"plan", "plan_t"};
+    for (int k = 0; k < 2; ++k) {                       // both plans are derived: a null one is refused
+        if (plans[k] == nullptr) return null_arg(fn, which[k]);
+        if (int rc = collate::check_plan(fn, which[k], plans[k], a->e_cap, a->e_cap)) return rc;
+    }
     const char* bad = nullptr;
     if (a->counts == nullptr) bad = "counts";
     else if (a->pooled_row_ptr == nullptr) bad = "pooled_row_ptr";
@@ -611,10 +463,7 @@ extern "C" int tfgx_static_pool_edges(const tfgx_static_pool_args* a, tfgx_strea
     p.nt = int32_t((a->e_cap + kTile - 1) / kTile);
     p.out_row = a->out_row, p.out_col = a->out_col, p.out_edge_id = a->out_edge_id, p.out_egi = a->out_edge_graph_index;
     p.out_w = a->out_w;
-    const tfgx_collate_plan* plans[2] = {a->plan, a->plan_t};
-    for (int k = 0; k < 2; ++k)
-        p.plan[k] = PlanDev{plans[k]->ds_row_ptr, plans[k]->ds_col, plans[k]->ds_perm, plans[k]->out_row_ptr, plans[k]->out_col,
-                            plans[k]->out_perm};
+    for (int k = 0; k < 2; ++k) p.plan[k] = collate::plan_dev(plans[k]);
     p.counts = a->counts;
     p.tile_cnt = ws.at<int32_t>(a->workspace, 0);
     p.tile_off = ws.at<int32_t>(a->workspace, 1);
@@ -655,8 +504,8 @@ extern "C" int tfgx_static_pool_gather_scale_rows_f32(const float* x, int64_t ld
     if (out == nullptr) return null_arg(fn, "out");
     const bool vec = ldx % 4 == 0 && ldo % 4 == 0 && aligned_to(x, 16) && aligned_to(out, 16);
     const int64_t F4 = vec ? F / 4 : 0;
-    pool_gather_scale_rows<<<grid_for(M * (F4 + F - 4 * F4), kBlock), kBlock, 0, as_stream(stream)>>>(x, ldx, n, idx, s, M, F, F4,
-                                                                                                     out, ldo);
-    TFGX_LAUNCH_CHECK("pool_gather_scale_rows");
+    gather_scale_rows<true><<<grid_for(M * (F4 + F - 4 * F4), kBlock), kBlock, 0, as_stream(stream)>>>(x, ldx, n, idx, s, M, F, F4,
+                                                                                                       out, ldo);
+    TFGX_LAUNCH_CHECK("gather_scale_rows<clamped>");
     return TFGX_OK;
 }

@@ -12,6 +12,7 @@
 // them is the ONE writer of the flag word.  No atomics: every output is a pure function of the inputs.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_compact.h"
 #include "tfgx_topk_keys.h"
 #include "../../include/tfgx_pool_static.h"
 #include "../../include/tfgx_rows3d.h"
@@ -26,7 +27,7 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 static_assert(kMaxGraph % (kBlock * kSelItems) == 0, "the cap is a whole number of ranking passes");
 static_assert(TFGX_ROWS3D_TOO_LONG == TFGX_STATIC_POOL_TOO_LONG, "the flag is ORed into counts[3] of a static batch");
 
-__device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return max(lo, min(v, hi)); }
+using compact::clampi;
 
 struct Rows3dParams {
     const int32_t* seg_ptr;

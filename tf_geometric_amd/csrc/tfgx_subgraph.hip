@@ -5,7 +5,7 @@
 // kept-node list, renumber them by position in that list, carry edge attributes along.  Here:
 //   count : node_map[n] (new id or -1, duplicates / out-of-range ids flagged), per-tile kept-edge counts, one scan;
 //           the host reads {kept count, flags} in ONE device -> host copy.
-//   emit  : order-stable compaction (wave ballot + mbcnt, tile offsets from the scan) of the relabelled edge list and
+//   emit  : order-stable compaction (the tile scheme of tfgx_compact.h, tile offsets from the scan) of the relabelled edge list and
 //           the original id of every kept edge; optionally the pooled graph's CSR plan DERIVED from the parent plan:
 //           tfgx_build_csr_by_dst is a stable sort by destination, so the kept edges of parent row node_index[j], walked
 //           in CSR order, are pooled row j in the order a rebuild would produce — no sort.
@@ -13,21 +13,14 @@
 // memset, no atomics, fixed-order reduction).  Integer atomics only (flags, duplicate detection); never on floats.
 #include "tfgx_common.h"
 #include "tfgx_host.h"
+#include "tfgx_compact.h"
+#include "tfgx_gather.h"
 #include <hipcub/hipcub.hpp>
 
 namespace tfgx {
 namespace {
 
-constexpr int kTileItems = 8;                          // edges per thread per tile
-constexpr int kTile = kBlock * kTileItems;             // 2048 edges per workgroup
-constexpr int kWavesPerBlock = kBlock / kWave;
-
-inline int64_t num_tiles(int64_t E) { return (E + kTile - 1) / kTile; }
-
-__device__ __forceinline__ int lane_prefix(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0));
-}
+using namespace compact;
 
 // node_map[v] = -1 for every node; tile_cnt[nt] = 0 (the scan's extra entry that becomes the total)
 __global__ void node_map_fill(int32_t* __restrict__ node_map, int64_t n, int32_t* __restrict__ tile_cnt_end)
@@ -61,48 +54,32 @@ __global__ void __launch_bounds__(kBlock) edge_tile_count(const int32_t* __restr
                                                           int64_t E, int64_t n, const int32_t* __restrict__ node_map,
                                                           int32_t* __restrict__ tile_cnt, int32_t* __restrict__ flags)
 {
-    __shared__ int32_t wave_cnt[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t base = int64_t(blockIdx.x) * kTile;
-    int cnt = 0, bad = 0;
-#pragma unroll
-    for (int it = 0; it < kTileItems; ++it) {
-        const int64_t e = base + it * kBlock + threadIdx.x;
-        bool keep = false;
-        if (e < E) {
+    int bad = 0;
+    tile_count(
+        [&](int64_t e) {
+            if (e >= E) return false;
             const int32_t r = row[e], c = col[e];
             const bool ok = (r >= 0) & (r < n) & (c >= 0) & (c < n);
             bad |= !ok;
-            keep = ok && node_map[r] >= 0 && node_map[c] >= 0;
-        }
-        cnt += __popcll(__ballot(keep));
-    }
-    if (__any(bad) && lane == 0) atomicOr(flags + 1, 1);
-    if (lane == 0) wave_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) t += wave_cnt[w];
-        tile_cnt[blockIdx.x] = t;
-    }
+            return ok && node_map[r] >= 0 && node_map[c] >= 0;
+        },
+        tile_cnt);
+    if (__any(bad) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(flags + 1, 1);
 }
 
-// Order-stable compaction: edge e = base + it * kBlock + wave * 64 + lane lands at
-// tile_off[tile] + (kept edges of earlier (it, wave) slots of the tile) + (kept lanes below it in its wave).
+// The order-stable compaction of tfgx_compact.h over the edges.  The store has NO `pos < n_kept` guard: the positions come from
+// this call's own count pass over the same node_map.
 __global__ void __launch_bounds__(kBlock) edge_tile_emit(const int32_t* __restrict__ row, const int32_t* __restrict__ col,
                                                          int64_t E, const int32_t* __restrict__ node_map,
                                                          const int32_t* __restrict__ tile_off,
                                                          int32_t* __restrict__ out_row, int32_t* __restrict__ out_col,
                                                          int32_t* __restrict__ out_edge_id, int32_t* __restrict__ rank)
 {
-    __shared__ int32_t slot_cnt[kTileItems][kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t base = int64_t(blockIdx.x) * kTile;
     uint64_t mask[kTileItems];
     int32_t nr[kTileItems], nc[kTileItems];
 #pragma unroll
     for (int it = 0; it < kTileItems; ++it) {
-        const int64_t e = base + it * kBlock + threadIdx.x;
+        const int64_t e = tile_item(it);
         nr[it] = -1;
         nc[it] = -1;
         if (e < E) {          // endpoints were validated by the count pass
@@ -110,28 +87,16 @@ __global__ void __launch_bounds__(kBlock) edge_tile_emit(const int32_t* __restri
             nc[it] = node_map[col[e]];
         }
         mask[it] = __ballot((nr[it] >= 0) & (nc[it] >= 0));
-        if (lane == 0) slot_cnt[it][wave] = __popcll(mask[it]);
     }
-    __syncthreads();
-    int32_t off = tile_off[blockIdx.x];
-#pragma unroll
-    for (int it = 0; it < kTileItems; ++it) {
-        int32_t before = 0, total = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) {
-            const int32_t c = slot_cnt[it][w];
-            before += (w < wave) ? c : 0;
-            total += c;
-        }
+    tile_positions(mask, tile_off, [&](int it, int32_t, int32_t pos) {
         if ((nr[it] >= 0) & (nc[it] >= 0)) {
-            const int64_t e = base + it * kBlock + threadIdx.x;
-            const int32_t pos = off + before + lane_prefix(mask[it]);
+            const int64_t e = tile_item(it);
             out_row[pos] = nr[it];
             out_col[pos] = nc[it];
             out_edge_id[pos] = int32_t(e);
             if (rank != nullptr) rank[e] = pos;
         }
-        off += total;
-    }
+    });
 }
 
 // G lanes per pooled row j (G | 64): walk parent row node_index[j] in CSR order, count the edges whose source is kept
@@ -140,8 +105,7 @@ __global__ void __launch_bounds__(kBlock) plan_row_count(const int32_t* __restri
                                                          const int32_t* __restrict__ node_index, int64_t m,
                                                          const int32_t* __restrict__ node_map, int32_t* __restrict__ cnt)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lig = lane % G, shift = lane - lig;
+    const int lig = threadIdx.x % G;
     const int64_t groups = int64_t(gridDim.x) * (kBlock / G);
     for (int64_t j = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / G; j < m; j += groups) {
         const int32_t o = node_index[j];
@@ -149,9 +113,7 @@ __global__ void __launch_bounds__(kBlock) plan_row_count(const int32_t* __restri
         int32_t c = 0;
         for (int32_t b = s; b < t; b += G) {
             const int32_t p = b + lig;
-            const bool keep = p < t && node_map[p_col[p]] >= 0;
-            const uint64_t bits = (__ballot(keep) >> shift) & ((G == 64) ? ~uint64_t(0) : ((uint64_t(1) << G) - 1));
-            c += __popcll(bits);
+            c += __popcll(group_bits<G>(p < t && node_map[p_col[p]] >= 0));
         }
         if (lig == 0) cnt[j] = c;
     }
@@ -168,8 +130,7 @@ __global__ void __launch_bounds__(kBlock) plan_row_emit(const int32_t* __restric
 {
     // a parent plan of ANOTHER edge list (the caller's mistake) must not write past the n_kept outputs nor read past rank
     const int32_t cap = *n_kept;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lig = lane % G, shift = lane - lig;
+    const int lig = threadIdx.x % G;
     const uint64_t below = (uint64_t(1) << lig) - 1;
     const int64_t groups = int64_t(gridDim.x) * (kBlock / G);
     for (int64_t j = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / G; j < m; j += groups) {
@@ -180,7 +141,7 @@ __global__ void __launch_bounds__(kBlock) plan_row_emit(const int32_t* __restric
             const int32_t p = b + lig;
             int32_t nc = -1;
             if (p < t) nc = node_map[p_col[p]];
-            const uint64_t bits = (__ballot(nc >= 0) >> shift) & ((G == 64) ? ~uint64_t(0) : ((uint64_t(1) << G) - 1));
+            const uint64_t bits = group_bits<G>(nc >= 0);
             if (nc >= 0) {
                 const int32_t q = pos + __popcll(bits & below);
                 const int32_t pe = p_perm[p];
@@ -190,40 +151,6 @@ __global__ void __launch_bounds__(kBlock) plan_row_emit(const int32_t* __restric
                 }
             }
             pos += __popcll(bits);
-        }
-    }
-}
-
-__global__ void gather_i32_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int64_t M,
-                                  int32_t* __restrict__ dst)
-{
-    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; i < M; i += stride) dst[i] = src[idx[i]];
-}
-
-// out[i, :] = x[idx[i], :] * s[idx[i]] (s == NULL: plain gather).  Row i = F4 float4 items + (F - 4 F4) scalar tail items.
-__global__ void gather_scale_rows(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ idx,
-                                  const float* __restrict__ s, int64_t M, int64_t F, int64_t F4,
-                                  float* __restrict__ out, int64_t ldo)
-{
-    const int64_t W = F4 + (F - 4 * F4);
-    const int64_t total = M * W;
-    int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (; t < total; t += stride) {
-        const int64_t i = t / W, q = t - i * W;
-        const int64_t r = idx[i];
-        const float sc = s != nullptr ? s[r] : 1.0f;
-        if (q < F4) {
-            float v[4];
-            load_vec<4>(x + r * ldx + 4 * q, v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] *= sc;
-            store_vec<4>(out + i * ldo + 4 * q, v);
-        } else {
-            const int64_t c = 4 * F4 + (q - F4);
-            out[i * ldo + c] = x[r * ldx + c] * sc;
         }
     }
 }
@@ -274,8 +201,6 @@ __global__ void __launch_bounds__(kBlock) gather_scale_backward(const float* __r
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 struct Layout {
     int64_t nt;
     size_t off_tile_cnt, off_tile_off, off_row_cnt, off_rank, off_temp, temp_bytes, total;
@@ -289,11 +214,7 @@ Layout layout(int64_t n, int64_t E, int64_t m, int with_plan)
     (void)n;
     Layout L;
     L.nt = num_tiles(E);
-    size_t scan_tiles = 0, scan_rows = 0;
-    const int32_t* in = nullptr;
-    int32_t* out = nullptr;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tiles, in, out, static_cast<int>(L.nt + 1));
-    if (with_plan) (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_rows, in, out, static_cast<int>(m + 1));
+    const size_t scan_tiles = scan_bytes(L.nt + 1), scan_rows = with_plan ? scan_bytes(m + 1) : 0;
     L.temp_bytes = align256(scan_tiles > scan_rows ? scan_tiles : scan_rows);
     L.off_tile_cnt = 0;
     L.off_tile_off = align256(sizeof(int32_t) * size_t(L.nt + 1));
@@ -439,8 +360,8 @@ extern "C" int tfgx_gather_i32(const int32_t* src, const int32_t* idx, int64_t M
     TFGX_REQUIRE(M >= 0, "negative size");
     if (M == 0) return TFGX_OK;
     TFGX_REQUIRE(src && idx && dst, "null pointer");
-    gather_i32_kernel<<<grid_for(M, kBlock), kBlock, 0, as_stream(stream)>>>(src, idx, M, dst);
-    TFGX_LAUNCH_CHECK("gather_i32_kernel");
+    gather_by_index<<<grid_for(M, kBlock), kBlock, 0, as_stream(stream)>>>(src, idx, M, dst);
+    TFGX_LAUNCH_CHECK("gather_by_index");
     return TFGX_OK;
 }
 
@@ -451,10 +372,10 @@ extern "C" int tfgx_gather_scale_rows_f32(const float* x, int64_t ldx, const int
     TFGX_REQUIRE(M >= 0 && F >= 0 && ldx >= F && ldo >= F, "bad size / leading dimension");
     if (M == 0 || F == 0) return TFGX_OK;
     TFGX_REQUIRE(x && idx && out, "null pointer");
-    const bool vec = ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out);
+    const bool vec = ldx % 4 == 0 && ldo % 4 == 0 && aligned_to(x, 16) && aligned_to(out, 16);
     const int64_t F4 = vec ? F / 4 : 0;
-    gather_scale_rows<<<grid_for(M * (F4 + F - 4 * F4), kBlock), kBlock, 0, as_stream(stream)>>>(x, ldx, idx, s, M, F, F4,
-                                                                                                 out, ldo);
+    gather_scale_rows<false><<<grid_for(M * (F4 + F - 4 * F4), kBlock), kBlock, 0, as_stream(stream)>>>(x, ldx, 0, idx, s, M, F,
+                                                                                                        F4, out, ldo);
     TFGX_LAUNCH_CHECK("gather_scale_rows");
     return TFGX_OK;
 }
@@ -469,8 +390,8 @@ extern "C" int tfgx_gather_scale_rows_backward_f32(const float* g, int64_t ldg, 
     TFGX_REQUIRE(ds == nullptr || (x != nullptr && ldx >= F), "ds needs x");
     if (n == 0 || (dx == nullptr && ds == nullptr)) return TFGX_OK;
     TFGX_REQUIRE(node_map != nullptr && (F == 0 || g != nullptr), "null pointer");
-    const bool vec = ldg % 4 == 0 && aligned16(g) && (dx == nullptr || (lddx % 4 == 0 && aligned16(dx))) &&
-                     (ds == nullptr || (ldx % 4 == 0 && aligned16(x)));
+    const bool vec = ldg % 4 == 0 && aligned_to(g, 16) && (dx == nullptr || (lddx % 4 == 0 && aligned_to(dx, 16))) &&
+                     (ds == nullptr || (ldx % 4 == 0 && aligned_to(x, 16)));
     const int64_t F4 = vec ? F / 4 : 0;
     gather_scale_backward<<<grid_for(n, kWavesPerBlock), kBlock, 0, as_stream(stream)>>>(g, ldg, node_map, n, x, ldx, s, F,
                                                                                           F4, dx, lddx, ds);
