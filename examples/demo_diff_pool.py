@@ -6,12 +6,19 @@ assignment GNN (GCN(128, relu) -> GCN(num_clusters)), a mean || max readout of t
 readouts concatenated, Dropout(0.5) -> Dense(num_classes); Adam(lr 1e-3), batches of 50 graphs.  NCI1 needs a download, so
 the data is the seeded NCI1-shaped stand-in of examples/demo_sag_pool_h.py.
 
-    python examples/demo_diff_pool.py [--steps 40] [--graphs 600]
+    python examples/demo_diff_pool.py [--steps 40] [--graphs 600] [--static] [--capture]
 
 Every S^T A S, S^T h product runs on the segmented-product kernel (include/tfgx_seggram.h); each pooled edge list carries its
 CSR plan, so the second level does not sort.  As in the reference, the pooled edge weights are differentiable in the
 assignment and train through the second level's GCNs: the GCN normalisation differentiates an edge_weight that requires
 grad (include/tfgx_normgrad.h).
+
+--static trains on fixed-shape batches instead: a GraphStore holds the graphs on the device, a StaticLoader hands on graph ids
+from a device cursor, collate_static assembles them at capacities the host computed once, and every level is the layer's
+pool_static (a static batch in, a static batch of B K rows and B K K edges out: include/tfgx_dense_pool_static.h) with the
+readouts the batches carry and a loss masked by graph_mask — no host read anywhere in the step.  --capture (implies --static)
+records ids -> batch -> both levels -> loss -> backward -> Adam once with tfg.CapturedTrainStep and replays it.  Without either
+flag the program is what it was.
 """
 import argparse
 import os
@@ -25,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tf_geometric_amd as tfg   # noqa: E402
 from tf_geometric_amd import autograd as AG   # noqa: E402
-from demo_sag_pool_h import make_dataset, make_batch, _glorot   # noqa: E402
+from demo_sag_pool_h import make_dataset, make_batch, _glorot, graph_store, make_static_step   # noqa: E402
 
 NUM_CLUSTERS = [20, 5]
 UNITS = 128
@@ -53,18 +60,29 @@ class GcnStack(object):
         return h
 
 
+class CachedGcnStack(GcnStack):
+    """The same stack handing the `cache` it is given to every GCN: pool_static passes the static batch's, which carries the
+    batch's plans (and, for weights that are not being trained, the normalised adjacency of the first GCN for the others)."""
+
+    def __call__(self, inputs, training=None, cache=None):
+        h, edge_index, edge_weight = inputs
+        for gcn in self.gcns:
+            h = gcn([h, edge_index, edge_weight], training=training, cache=cache)
+        return h
+
+
 class DensePoolModel(object):
     """detach_pooled_weights: hand the pooled edge weights to the next level as constants — for a pooling layer that refuses
     an edge_weight that requires grad (MinCutPool); DiffPool trains through them."""
 
-    def __init__(self, pool_cls, num_features, num_classes, seed=0, detach_pooled_weights=False):
+    def __init__(self, pool_cls, num_features, num_classes, seed=0, detach_pooled_weights=False, stack=GcnStack):
         dev = torch.device("cuda")
         self.detach_pooled_weights = detach_pooled_weights
         self.gnns, self.pools = [], []
         for level, k in enumerate(NUM_CLUSTERS):
             f = num_features if level == 0 else UNITS
-            feature = GcnStack(f, [UNITS, UNITS], True, seed + 10 * level)
-            assign = GcnStack(f, [UNITS, k], False, seed + 10 * level + 5)
+            feature = stack(f, [UNITS, UNITS], True, seed + 10 * level)
+            assign = stack(f, [UNITS, k], False, seed + 10 * level + 5)
             pool = pool_cls(feature, assign, UNITS, k, activation=torch.relu)
             pool.trainable(True)
             self.gnns += [feature, assign]
@@ -96,6 +114,66 @@ class DensePoolModel(object):
         logits = AG.linear(g, *self.head)
         return (logits, losses) if return_losses else logits
 
+    def static(self, batch, training=False, return_losses=False):
+        """The model on a StaticBatchGraph: one row of logits per SLOT (dead slots: the biases alone).  Level by level the
+        pooled batch replaces its parent; mean || max readouts through the graph plan each batch carries."""
+        h, readouts, losses = batch.x, [], []
+        for pool in self.pools:
+            if return_losses:
+                batch, pair = pool.pool_static(h, batch, training=training, return_losses=True)
+                losses.append(pair)
+            else:
+                batch = pool.pool_static(h, batch, training=training)
+            if self.detach_pooled_weights:
+                batch.edge_weight = batch.edge_weight.detach()
+            h = batch.x
+            readouts.append(torch.cat([batch.readout(h, "mean"), batch.readout(h, "max")], dim=-1))
+        g = torch.cat(readouts, dim=-1)
+        if training:
+            g = torch.nn.functional.dropout(g, 0.5, training=True)
+        logits = AG.linear(g, *self.head)
+        return (logits, losses) if return_losses else logits
+
+
+def static_loss(with_losses):
+    """loss(model, batch): the mean cross-entropy over the LIVE slots (a dead slot holds graph 0's label: torch.where on
+    graph_mask) plus, with_losses, every level's cut and orthogonality loss (means over the live slots themselves)."""
+    def loss(model, batch, training=True):
+        out = model.static(batch, training=training, return_losses=with_losses)
+        logits, losses = out if with_losses else (out, [])
+        per_slot = torch.nn.functional.cross_entropy(logits, batch.y.reshape(-1), reduction="none")
+        zero = torch.zeros((), dtype=per_slot.dtype, device=per_slot.device)
+        total = torch.where(batch.graph_mask, per_slot, zero).sum() / batch.counts[0].clamp(min=1).to(per_slot.dtype)
+        for cut, orth in losses:
+            total = total + cut + orth
+        return total
+    return loss
+
+
+def run_static(pool_cls, with_losses, detach_pooled_weights, data, args):
+    """The --static / --capture route: the steps of run() over fixed-shape batches."""
+    model = DensePoolModel(pool_cls, data.num_features, data.num_classes, seed=args.seed,
+                           detach_pooled_weights=detach_pooled_weights, stack=CachedGcnStack)
+    store = graph_store(data, range(len(data.graphs)))
+    loader = store.static_loader(args.batch_size, shuffle=True, seed=args.seed + 1)
+    cap = store.static_capacities(args.batch_size)
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr, capturable=args.capture)
+    step = make_static_step(model, store, loader, cap, opt, args.capture, loss=static_loss(with_losses))
+    print("batches: collate_static{}; capacities: {} rows and {} edges for {} slots, pooled to {} and {} rows".format(
+        ", replayed" if args.capture else "", cap.n_cap, cap.e_cap, cap.batch_size,
+        *[cap.batch_size * k for k in NUM_CLUSTERS]), flush=True)
+    t0 = time.perf_counter()
+    loss = None
+    for i in range(args.steps):
+        if i and i % loader.steps_per_epoch == 0:
+            loader.reshuffle(args.seed + 1 + i)                   # in place: the replay reads the new order
+        loss = step()
+        if i % 5 == 0 or i == args.steps - 1:
+            value = float(loss.detach())                          # the one read, on the steps that print
+            print("step {:4d}  loss {:.4f}  ({:.1f} ms / step)".format(i, value, (time.perf_counter() - t0) * 1e3 / (i + 1)),
+                  flush=True)
+    assert torch.isfinite(loss), "the loss diverged"
+
 
 def run(pool_cls, with_losses, title, detach_pooled_weights=False):
     p = argparse.ArgumentParser(description=title)
@@ -104,9 +182,13 @@ def run(pool_cls, with_losses, title, detach_pooled_weights=False):
     p.add_argument("--batch-size", type=int, default=50)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--static", action="store_true", help="fixed-shape batches: collate_static and the layers' pool_static")
+    p.add_argument("--capture", action="store_true", help="replay the whole step from one hipGraph (implies --static)")
     args = p.parse_args()
     torch.manual_seed(args.seed)
     data = make_dataset(args.graphs, args.seed)
+    if args.static or args.capture:
+        return run_static(pool_cls, with_losses, detach_pooled_weights, data, args)
     model = DensePoolModel(pool_cls, data.num_features, data.num_classes, seed=args.seed,
                            detach_pooled_weights=detach_pooled_weights)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)

@@ -5,7 +5,10 @@ The model of examples/demo_diff_pool.py with MinCutPool layers (20 and 5 cluster
 loss plus, per level, the cut loss and the orthogonality loss that the layer's loss callable returns.  Data: the seeded
 NCI1-shaped stand-in of examples/demo_sag_pool_h.py.
 
-    python examples/demo_min_cut_pool.py [--steps 40] [--graphs 600]
+    python examples/demo_min_cut_pool.py [--steps 40] [--graphs 600] [--static] [--capture]
+
+--static / --capture: the fixed-shape route of examples/demo_diff_pool.py with MinCutPool.pool_static; the two losses of every
+level are means over the live slots and are part of the replayed step.
 
 Unlike the DiffPool demo, the pooled edge weights are detached before they enter the next level
 (detach_pooled_weights=True): MinCutPool normalises its edge weights with raw kernel launches (adj_norm_edge) and still

@@ -518,6 +518,31 @@ ROWS3D_SIGNATURES = {
     "tfgx_segment_rows_3d_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P]),
 }
 
+class DensePoolStaticArgs(ctypes.Structure):
+    """struct tfgx_dense_pool_static_args (include/tfgx_dense_pool_static.h)."""
+    _fields_ = [
+        ("P", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("graph_mask", ctypes.c_void_p), ("parent_counts", ctypes.c_void_p),
+        ("B", ctypes.c_int64), ("K", ctypes.c_int64), ("drop_diagonal", ctypes.c_int32),
+        ("n_cap_out", ctypes.c_int64), ("e_cap", ctypes.c_int64), ("sinks", ctypes.c_int64), ("sink_degree", ctypes.c_int64),
+        ("pooled_row_ptr", ctypes.c_void_p), ("node_index", ctypes.c_void_p), ("node_graph_index", ctypes.c_void_p),
+        ("node_map", ctypes.c_void_p),
+        ("out_row", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_edge_src", ctypes.c_void_p),
+        ("out_edge_graph_index", ctypes.c_void_p),
+        ("plan", ctypes.POINTER(CollatePlan)), ("plan_t", ctypes.POINTER(CollatePlan)),
+        ("counts", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+# include/tfgx_dense_pool_static.h (the pooled batch of one fixed-shape DiffPool / MinCutPool level: S^T A S blocks in, static batch out)
+DENSE_POOL_STATIC_ABI_VERSION = 1
+DENSE_POOL_STATIC_MAX_K = 64             # TFGX_DENSE_POOL_STATIC_MAX_K: TFGX_SEGGRAM_MAX_K, a row of a block is one wave ballot
+DENSE_POOL_STATIC_MAX_SLOTS = 1 << 20    # TFGX_DENSE_POOL_STATIC_MAX_SLOTS
+DENSE_POOL_STATIC_SIGNATURES = {
+    "tfgx_dense_pool_static_version": (ctypes.c_int, []),
+    "tfgx_dense_pool_static_workspace_bytes": (_SZ, [_I64]),
+    "tfgx_dense_pool_static": (ctypes.c_int, [ctypes.POINTER(DensePoolStaticArgs), _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry (DESIGN.md, "Adding a header").
@@ -542,6 +567,7 @@ ABIS = (
     Abi("tfgx_collate_static.h", "tfgx_static_batch_version", COLLATE_STATIC_ABI_VERSION, COLLATE_STATIC_SIGNATURES, ()),
     Abi("tfgx_pool_static.h", "tfgx_static_pool_version", STATIC_POOL_ABI_VERSION, STATIC_POOL_SIGNATURES, ()),
     Abi("tfgx_rows3d.h", "tfgx_rows3d_version", ROWS3D_ABI_VERSION, ROWS3D_SIGNATURES, ()),
+    Abi("tfgx_dense_pool_static.h", "tfgx_dense_pool_static_version", DENSE_POOL_STATIC_ABI_VERSION, DENSE_POOL_STATIC_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module
@@ -549,7 +575,7 @@ STRUCTS = {
     "tfgx_reduce_args": ReduceArgs, "tfgx_gat_args": GatArgs, "tfgx_hub_lists": HubLists,
     "tfgx_gat_backward_args": GatBackwardArgs, "tfgx_drop_edge_plan": DropEdgePlan, "tfgx_collate_plan": CollatePlan,
     "tfgx_collate_args": CollateArgs, "tfgx_static_batch_args": CollateStaticArgs,
-    "tfgx_static_pool_args": StaticPoolArgs,
+    "tfgx_static_pool_args": StaticPoolArgs, "tfgx_dense_pool_static_args": DensePoolStaticArgs,
 }
 
 

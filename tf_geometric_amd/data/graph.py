@@ -412,6 +412,34 @@ class StaticBatchGraph(BatchGraph):
         self.graph_row_ptr = None       # int32 [B + 2]: the slots' row offsets, the live total, n_cap (the graph plan's row_ptr)
         self.node_index = None          # a pooled batch (nn.sag_pool_static): pooled row -> parent row, -1 for a dead row
         self.edge_id = None             # ... and pooled edge -> parent edge, -1 for a padded one
+        self.edge_src = None            # a dense-pooled batch (nn.diff_pool_static): pooled edge -> its entry of S^T A S, or -1
+        self._degree_bound = None       # a dense-pooled batch and what is pooled from it: the most edges of a live row (K)
+
+    def max_degree(self):
+        """A bound of the edges of a live row, in either direction: the store's largest in- / out-degree for a batch of the
+        store's own graphs (host work, once per store), num_clusters once a dense pool has replaced them."""
+        if self._degree_bound is not None:
+            return int(self._degree_bound)
+        return max(self._store._max_degrees())
+
+    def dense_pooled_capacities(self, num_clusters, drop_diagonal=False):
+        """StaticBatchCapacities of this batch pooled by nn.diff_pool_static / nn.min_cut_pool_static (drop_diagonal=True) into
+        K = num_clusters clusters per graph: host arithmetic, no device.  Every live slot becomes exactly K rows and at most
+        K K edges (K (K - 1) without the diagonal), so max_nodes = B K and max_edges = B K K are reached by a batch of B live
+        slots with dense blocks and exceeded by none; the sink degree d stays and sinks = max(1, ceil(max_edges / d)).
+        ValueError: a K that is no integer of at least 1, sizes beyond int32."""
+        cap = self.capacities
+        K = num_clusters
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+            raise ValueError("dense_pooled_capacities: num_clusters must be an integer of at least 1, got {!r}".format(K))
+        B, K, d = int(cap.batch_size), int(K), int(cap.sink_degree)
+        max_nodes = B * K
+        max_edges = B * K * (K - 1 if drop_diagonal else K)
+        sinks = max(1, -(-max_edges // d))
+        if max_nodes + sinks >= (1 << 31) - 1 or B * K * K >= (1 << 31) - 1:
+            raise ValueError("dense_pooled_capacities: {} slots of {} clusters ({} rows + {} sinks, {} edges) do not fit "
+                             "int32".format(B, K, max_nodes, sinks, max_edges))
+        return type(cap)(B, max_nodes, max_edges, d, sinks, max_nodes + sinks, max_edges)
 
     def readout(self, h, op="mean"):
         """[B, F]: the `op` ("mean" / "sum" / "max" / "min") of h over the nodes of each slot, through the graph plan the batch

@@ -2,6 +2,7 @@
 """DiffPool as a layer object (reference: layers/pool/diff_pool.py).  inputs = [x, edge_index, edge_weight, node_graph_index]
 -> [pooled_x, pooled_edge_index, pooled_edge_weight, pooled_node_graph_index]."""
 from ...nn.pool.diff_pool import diff_pool
+from ...nn.pool.dense_pool_static import diff_pool_static
 from .._base import Layer
 
 
@@ -56,3 +57,10 @@ class DiffPool(DensePool):
         x, edge_index, edge_weight, node_graph_index = inputs
         return diff_pool(x, edge_index, edge_weight, node_graph_index, self.feature_gnn, self.assign_gnn, self.num_clusters,
                          bias=self.bias, activation=self.activation, training=training, cache=cache, num_graphs=num_graphs)
+
+    def pool_static(self, x, batch, training=None):
+        """The layer on a StaticBatchGraph (GraphStore.collate_static's, or an earlier pool_static's): the pooled
+        StaticBatchGraph of nn.diff_pool_static with this layer's GNNs, clusters, bias and activation.  No host read;
+        capturable."""
+        return diff_pool_static(x, batch, self.feature_gnn, self.assign_gnn, self.num_clusters, bias=self.bias,
+                                activation=self.activation, training=training)

@@ -2,6 +2,7 @@
 """MinCutPool as a layer object (reference: layers/pool/min_cut_pool.py).  inputs = [x, edge_index, edge_weight,
 node_graph_index] -> [pooled_x, pooled_edge_index, pooled_edge_weight, pooled_node_graph_index]."""
 from ...nn.pool.min_cut_pool import min_cut_pool
+from ...nn.pool.dense_pool_static import min_cut_pool_static
 from .diff_pool import DensePool
 
 
@@ -40,3 +41,19 @@ class MinCutPool(DensePool):
         if return_losses:
             return outputs, loss_func()
         return outputs
+
+    def pool_static(self, x, batch, training=None, return_loss_func=False, return_losses=False):
+        """The layer on a StaticBatchGraph: the pooled StaticBatchGraph of nn.min_cut_pool_static (with the loss callable or
+        the two losses, means over the live slots, when asked for).  `losses` evaluates the latest call's.  No host read;
+        capturable."""
+        if return_loss_func and return_losses:
+            raise ValueError("return_loss_func and return_losses cannot be set to True at the same time")
+        pooled, loss_func = min_cut_pool_static(x, batch, self.feature_gnn, self.assign_gnn, self.num_clusters, bias=self.bias,
+                                                activation=self.activation, gnn_use_normed_edge=self.gnn_use_normed_edge,
+                                                return_loss_func=True, training=training)
+        self.loss_func = loss_func
+        if return_loss_func:
+            return pooled, loss_func
+        if return_losses:
+            return pooled, loss_func()
+        return pooled

@@ -13,5 +13,7 @@ from .pool import mean_pool, sum_pool, max_pool, min_pool, topk_pool, sag_pool, 
 from .pool import sag_pool_static, topk_pool_static
 from .pool import sort_pool_3d, sort_pool_3d_route, sort_pool_static
 from .pool import diff_pool, diff_pool_coarsen, min_cut_pool, min_cut_pool_coarsen, min_cut_pool_compute_losses
+from .pool import (diff_pool_static, diff_pool_coarsen_static, min_cut_pool_static, min_cut_pool_coarsen_static,
+                   min_cut_pool_compute_losses_static)
 from .sampling import drop_edge
 from .link import edge_dot

@@ -10,3 +10,5 @@ from .cluster_pool import cluster_pool
 from .asap import asap
 from .diff_pool import diff_pool, diff_pool_coarsen
 from .min_cut_pool import min_cut_pool, min_cut_pool_coarsen, min_cut_pool_compute_losses
+from .dense_pool_static import (diff_pool_static, diff_pool_coarsen_static, min_cut_pool_static, min_cut_pool_coarsen_static,
+                                min_cut_pool_compute_losses_static)

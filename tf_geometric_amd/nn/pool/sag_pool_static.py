@@ -172,21 +172,32 @@ def sag_pool_static(x, batch, score_gnn, k=None, ratio=None, score_activation=No
                               batch._store_len, given_ids=batch._given_ids)
     pooled._store, pooled.graph_row_ptr = store, sel.pooled_row_ptr
     pooled.node_index, pooled.edge_id = sel.node_index, edge_id
+    pooled._degree_bound = batch._degree_bound
+    # no pooled row is longer than its parent row, and a sink holds sink_degree edges as before: the rule of collate_static
+    attach_static_plans(pooled, store, plans, arange, batch.max_degree())
+    return pooled
+
+
+def attach_static_plans(pooled, store, plans, arange, max_degree):
+    """Link the two edge plans a static pool derived for `pooled`, and the graph plan over its graph_row_ptr, and attach and
+    cache all three the way collate_static does.  `max_degree` bounds the edges of a live row of either edge plan; with the
+    sink degree it decides, by plan.hub_policy's threshold for these capacities, whether both are marked as having no hub rows
+    and no walk order.  `arange`: the store's identity array, at least n_cap + 1 long."""
+    cap, ei, ngi = pooled.capacities, pooled.edge_index, pooled.node_graph_index
+    B = cap.batch_size
     new_plan, new_plan_t = plans
     new_plan._edge_index = ei
     new_plan._transposed, new_plan_t._transposed = new_plan_t, new_plan
-    # no pooled row is longer than its parent row, and a sink holds sink_degree edges as before: the rule of collate_static
-    thr, _ = hub_policy(e_cap, cap.n_cap)
-    if max(max(store._max_degrees()), cap.sink_degree) <= thr:
+    thr, _ = hub_policy(cap.e_cap, cap.n_cap)
+    if max(max_degree, cap.sink_degree) <= thr:
         for pl in plans:
             pl.hub_threshold, pl._hub, pl._row_order = thr, False, False
     attach_plan(ei, new_plan)
     pooled.cache[CACHE_KEY_PLAN] = new_plan
     nodes = arange[:cap.n_cap]
-    graph_plan = CsrPlan(sel.pooled_row_ptr, nodes, nodes, B + 1, cap.n_cap, cap.n_cap)
-    graph_plan._transposed = CsrPlan(arange[:cap.n_cap + 1], sel.node_graph_index, nodes, cap.n_cap, B + 1, cap.n_cap)
+    graph_plan = CsrPlan(pooled.graph_row_ptr, nodes, nodes, B + 1, cap.n_cap, cap.n_cap)
+    graph_plan._transposed = CsrPlan(arange[:cap.n_cap + 1], ngi, nodes, cap.n_cap, B + 1, cap.n_cap)
     graph_plan._transposed._transposed = graph_plan
     for pl, rows in ((graph_plan, B + 1), (graph_plan._transposed, cap.n_cap)):
         pl.hub_threshold, pl._hub, pl._row_order = hub_policy(cap.n_cap, rows)[0], False, False
-    pooled.cache[CACHE_KEY_GRAPH_PLAN] = (sel.node_graph_index, sel.node_graph_index._version, graph_plan)
-    return pooled
+    pooled.cache[CACHE_KEY_GRAPH_PLAN] = (ngi, ngi._version, graph_plan)
