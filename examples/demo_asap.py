@@ -5,10 +5,17 @@ Same model: 3 x (GCN(64, relu) -> ASAP(ratio 0.5, drop_rate 0.1)), a mean || max
 readouts summed, then Dense(64, relu) -> Dropout(0.5) -> Dense(num_classes).  The data is the seeded NCI1-shaped stand-in of
 examples/demo_sag_pool_h.py (NCI1 itself needs a download).
 
-    python examples/demo_asap.py [--epochs 20] [--graphs 4000]
+    python examples/demo_asap.py [--epochs 20] [--graphs 4000] [--static] [--capture]
 
 Every level's attention is one fused launch, every coarsened adjacency a sparse S^T A S; each pooled edge list carries its CSR
 plan, so the GCN of the next level does not sort.
+
+--static trains on fixed-shape batches instead: a GraphStore holds the graphs on the device, a StaticLoader hands on graph ids
+from a device cursor, collate_static assembles them at capacities the host computed once, and every level is ASAP.pool_static (a
+static batch in, a static batch out whose capacities shrink level by level: include/tfgx_asap_static.h) with the readouts the
+batches carry and a loss masked by graph_mask — no host read anywhere in the step.  --capture (implies --static) records
+ids -> batch -> three levels -> loss -> backward -> Adam once with tfg.CapturedTrainStep and replays it; the attention dropout
+reads a device seed, so every replay draws new masks.  Without either flag the program is what it was.
 """
 import argparse
 import os
@@ -22,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tf_geometric_amd as tfg   # noqa: E402
 from tf_geometric_amd import autograd as AG   # noqa: E402
-from demo_sag_pool_h import make_dataset, make_batch, evaluate, _glorot   # noqa: E402,F401
+from demo_sag_pool_h import make_dataset, make_batch, evaluate, _glorot, graph_store, make_static_step   # noqa: E402,F401
 
 UNITS = 64
 
@@ -70,6 +77,51 @@ class ASAPModel(object):
             h = torch.nn.functional.dropout(h, 0.5, training=True)
         return AG.linear(h, k1, b1)
 
+    def static(self, batch, training=False, levels=None):
+        """The model on a StaticBatchGraph: one row of logits per SLOT (dead slots: the biases alone).  Level by level the pooled
+        batch replaces its parent (and is appended to `levels` when a list is given)."""
+        h, out = batch.x, None
+        for gcn, asap in zip(self.gcns, self.asaps):
+            h = gcn([h, batch.edge_index, batch.edge_weight], cache=batch.cache, training=training)
+            batch = asap.pool_static(h, batch, training=training)
+            h = batch.x
+            if levels is not None:
+                levels.append(batch)
+            readout = torch.cat([batch.readout(h, "mean"), batch.readout(h, "max")], dim=-1)
+            out = readout if out is None else out + readout
+        (k0, b0), (k1, b1) = self.mlp
+        h = AG.linear(out, k0, b0, tfg._lib.ACT_RELU)
+        if training:
+            h = torch.nn.functional.dropout(h, 0.5, training=True)
+        return AG.linear(h, k1, b1)
+
+
+def static_loss(model, batch, training=True):
+    """Mean cross-entropy over the LIVE slots (a dead slot holds graph 0's label: torch.where on graph_mask)."""
+    per_slot = torch.nn.functional.cross_entropy(model.static(batch, training=training), batch.y.reshape(-1), reduction="none")
+    zero = torch.zeros((), dtype=per_slot.dtype, device=per_slot.device)
+    return torch.where(batch.graph_mask, per_slot, zero).sum() / batch.counts[0].clamp(min=1).to(per_slot.dtype)
+
+
+def train_static(model, data, train_idx, test_batches, args):
+    """The --static / --capture route: the epochs of main() over fixed-shape batches."""
+    store = graph_store(data, train_idx)
+    loader = store.static_loader(args.batch_size, shuffle=True, seed=args.seed + 1)
+    cap = store.static_capacities(args.batch_size)
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr, capturable=args.capture)
+    step = make_static_step(model, store, loader, cap, opt, args.capture, loss=static_loss)
+    print("batches: collate_static{}; capacities: {} rows and {} edges for {} slots".format(
+        ", replayed" if args.capture else "", cap.n_cap, cap.e_cap, cap.batch_size), flush=True)
+    for epoch in range(args.epochs):
+        if epoch:
+            loader.reshuffle(args.seed + 1 + epoch)           # in place: the replay reads the new order
+        t0 = time.perf_counter()
+        losses = torch.stack([step().detach().clone() for _ in range(loader.steps_per_epoch)])
+        loss = float(losses.mean().item())                    # the one read of the epoch
+        ms = (time.perf_counter() - t0) * 1e3 / loader.steps_per_epoch
+        print("epoch {:3d}  loss {:.6f}  test accuracy {:.4f}  ({:.2f} ms / step)".format(
+            epoch, loss, evaluate(model, test_batches), ms), flush=True)
+
 
 def train_step(model, opt, batch):
     x, ei, gid, y, num_graphs = batch
@@ -88,6 +140,8 @@ def main():
     p.add_argument("--batch-size", type=int, default=512)
     p.add_argument("--lr", type=float, default=5e-4)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--static", action="store_true", help="fixed-shape batches: collate_static and ASAP.pool_static")
+    p.add_argument("--capture", action="store_true", help="replay the whole step from one hipGraph (implies --static)")
     args = p.parse_args()
     torch.manual_seed(args.seed)
     data = make_dataset(args.graphs, args.seed)
@@ -95,6 +149,8 @@ def main():
     train_idx = np.arange(n_test, len(data.graphs))
     test_batches = [make_batch(data, list(range(i, min(i + args.batch_size, n_test)))) for i in range(0, n_test, args.batch_size)]
     model = ASAPModel(data.num_features, data.num_classes, seed=args.seed)
+    if args.static or args.capture:
+        return train_static(model, data, train_idx, test_batches, args)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     rng = np.random.Generator(np.random.PCG64(args.seed + 1))
     for epoch in range(args.epochs):

@@ -16,7 +16,7 @@ SOURCES = ["tfgx_plan.hip", "tfgx_reduce.hip", "tfgx_norm.hip", "tfgx_attn.hip",
            "tfgx_topk.hip", "tfgx_fused.hip", "tfgx_poolgrad.hip", "tfgx_subgraph.hip", "tfgx_plan_ext.hip", "tfgx_reduce_h16.hip", "tfgx_fused_h16.hip",
            "tfgx_dropedge.hip", "tfgx_linkpred.hip", "tfgx_lstm.hip", "tfgx_set2set.hip", "tfgx_asap.hip", "tfgx_seggram.hip",
            "tfgx_normgrad.hip", "tfgx_collate.hip", "tfgx_nbrblock.hip", "tfgx_samplereduce.hip", "tfgx_nbrstatic.hip", "tfgx_collate_static.hip",
-           "tfgx_pool_static.hip", "tfgx_rows3d.hip", "tfgx_dense_pool_static.hip"]
+           "tfgx_pool_static.hip", "tfgx_rows3d.hip", "tfgx_dense_pool_static.hip", "tfgx_asap_static.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("TFGX_EXTRA_HIPCC_FLAGS", "").split()      # developer A/B switches (e.g. -DTFGX_PREFETCH_INDEX=0)

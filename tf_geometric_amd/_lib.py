@@ -543,6 +543,36 @@ DENSE_POOL_STATIC_SIGNATURES = {
     "tfgx_dense_pool_static": (ctypes.c_int, [ctypes.POINTER(DensePoolStaticArgs), _P]),
 }
 
+class AsapStaticEdgesArgs(ctypes.Structure):
+    """struct tfgx_asapstatic_edges_args (include/tfgx_asap_static.h)."""
+    _fields_ = [
+        ("P", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("pooled_row_ptr", ctypes.c_void_p),
+        ("B", ctypes.c_int64), ("K", ctypes.c_int64),
+        ("n_cap_out", ctypes.c_int64), ("e_cap", ctypes.c_int64), ("sinks", ctypes.c_int64), ("sink_degree", ctypes.c_int64),
+        ("out_row", ctypes.c_void_p), ("out_col", ctypes.c_void_p), ("out_edge_src", ctypes.c_void_p),
+        ("out_edge_graph_index", ctypes.c_void_p),
+        ("plan", ctypes.POINTER(CollatePlan)), ("plan_t", ctypes.POINTER(CollatePlan)),
+        ("counts", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+# include/tfgx_asap_static.h (one fixed-shape ASAP level: attention with absent self-loops, the dense assignment, the ragged
+# pooled edge list with both plans)
+ASAPSTATIC_ABI_VERSION = 1
+ASAPSTATIC_MAX_K = 64                    # TFGX_ASAPSTATIC_MAX_K: TFGX_SEGGRAM_MAX_K, a row of a block is one wave ballot
+ASAPSTATIC_MAX_FEATURES = 256            # TFGX_ASAPSTATIC_MAX_FEATURES: TFGX_ASAP_MAX_FEATURES, the same kernel
+ASAPSTATIC_MAX_SLOTS = 1 << 20           # TFGX_ASAPSTATIC_MAX_SLOTS
+ASAPSTATIC_SIGNATURES = {
+    "tfgx_asapstatic_version": (ctypes.c_int, []),
+    "tfgx_asapstatic_attend_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _F32, _U64, _P, _I32, _P, _I64, _P,
+                                                  _P, _P, _P, _P, _P]),
+    "tfgx_asapstatic_attend_backward_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P,
+                                                           _P]),
+    "tfgx_asapstatic_assign_f32": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _P]),
+    "tfgx_asapstatic_edges_workspace_bytes": (_SZ, [_I64]),
+    "tfgx_asapstatic_edges": (ctypes.c_int, [ctypes.POINTER(AsapStaticEdgesArgs), _P]),
+}
+
 # One record per header under include/, tfgx.h first: the file, its version function with the version bound here, its table, and
 # the (function, value) pairs of the constants the library was built with.  bind() and tests/test_abi_registry.py walk this
 # registry; a new header is one more entry (DESIGN.md, "Adding a header").
@@ -568,6 +598,7 @@ ABIS = (
     Abi("tfgx_pool_static.h", "tfgx_static_pool_version", STATIC_POOL_ABI_VERSION, STATIC_POOL_SIGNATURES, ()),
     Abi("tfgx_rows3d.h", "tfgx_rows3d_version", ROWS3D_ABI_VERSION, ROWS3D_SIGNATURES, ()),
     Abi("tfgx_dense_pool_static.h", "tfgx_dense_pool_static_version", DENSE_POOL_STATIC_ABI_VERSION, DENSE_POOL_STATIC_SIGNATURES, ()),
+    Abi("tfgx_asap_static.h", "tfgx_asapstatic_version", ASAPSTATIC_ABI_VERSION, ASAPSTATIC_SIGNATURES, ()),
 )
 
 # C struct name -> its ctypes mirror: every ctypes.Structure of this module
@@ -576,6 +607,7 @@ STRUCTS = {
     "tfgx_gat_backward_args": GatBackwardArgs, "tfgx_drop_edge_plan": DropEdgePlan, "tfgx_collate_plan": CollatePlan,
     "tfgx_collate_args": CollateArgs, "tfgx_static_batch_args": CollateStaticArgs,
     "tfgx_static_pool_args": StaticPoolArgs, "tfgx_dense_pool_static_args": DensePoolStaticArgs,
+    "tfgx_asapstatic_edges_args": AsapStaticEdgesArgs,
 }
 
 

@@ -1560,9 +1560,11 @@ def plan_rows(plan):
     return plan._rows64
 
 
-def asap_attend_forward(plan, x, sq, sh, bias, drop_rate=0.0, seed=0, bad_flag=None):
+def asap_attend_forward(plan, x, sq, sh, bias, drop_rate=0.0, seed=0, bad_flag=None, skip_self_loops=False):
     """One tfgx_asap_attend_f32 call on a square plan: (c [N, F], p [E], p_self [N], p_drop, p_self_drop) — the last two are
-    None without dropout (they would equal p and p_self)."""
+    None without dropout (they would equal p and p_self).  skip_self_loops, or a seed that is a device tensor (int64 [1]:
+    nn.conv.gat.new_drop_seed inside a capture), takes tfgx_asapstatic_attend_f32 — the same kernel body with edges row == col
+    absent and the seed read from device memory."""
     lib = L.require_gpu()
     x, ldx = L.row_major_2d(x)
     N, E, F = plan.n_dst, plan.num_edges, int(x.shape[1])
@@ -1573,8 +1575,16 @@ def asap_attend_forward(plan, x, sq, sh, bias, drop_rate=0.0, seed=0, bad_flag=N
     pd = pds = None
     if drop_rate > 0.0:
         pd, pds = torch.empty_like(p), torch.empty_like(p_self)
+    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    seed = 0 if seed_dev is not None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    if skip_self_loops or seed_dev is not None:
+        L.check(lib.tfgx_asapstatic_attend_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(x), ldx, F, L.ptr(sq), L.ptr(sh),
+                                               L.ptr(bias), float(drop_rate), seed, L.ptr(seed_dev), int(bool(skip_self_loops)),
+                                               L.ptr(c), max(F, 1), L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds),
+                                               L.ptr(bad_flag), L.stream_ptr()), "tfgx_asapstatic_attend_f32")
+        return c, p, p_self, pd, pds
     L.check(lib.tfgx_asap_attend_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(x), ldx, F, L.ptr(sq), L.ptr(sh),
-                                     L.ptr(bias), float(drop_rate), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(c), max(F, 1),
+                                     L.ptr(bias), float(drop_rate), seed, L.ptr(c), max(F, 1),
                                      L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds), L.ptr(bad_flag), L.stream_ptr()),
             "tfgx_asap_attend_f32")
     return c, p, p_self, pd, pds
@@ -1587,11 +1597,11 @@ class _AsapAttend(torch.autograd.Function):
     dp_e = <g_i, x[col_e]> on the SDDMM kernel (both existing), then ONE launch for the softmax / leaky-relu backward."""
 
     @staticmethod
-    def forward(ctx, plan, x, sq, sh, bias, drop_rate, seed):
+    def forward(ctx, plan, x, sq, sh, bias, drop_rate, seed, skip_self_loops=False):
         xd = x.detach()
         sqd, shd, bd = sq.detach().contiguous(), sh.detach().contiguous(), bias.detach().contiguous()
-        c, p, p_self, pd, pds = asap_attend_forward(plan, xd, sqd, shd, bd, drop_rate, seed)
-        ctx.plan = plan
+        c, p, p_self, pd, pds = asap_attend_forward(plan, xd, sqd, shd, bd, drop_rate, seed, skip_self_loops=skip_self_loops)
+        ctx.plan, ctx.skip = plan, bool(skip_self_loops)
         ctx.save_for_backward(xd, sqd, shd, bd, p, p_self, pd, pds)
         pw, pws = (p, p_self) if pd is None else (pd, pds)
         ctx.mark_non_differentiable(pw, pws)
@@ -1608,20 +1618,27 @@ class _AsapAttend(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         gx, dp, dps = _aggregate_backward(plan, False, x, pw, pws, g, need_x, need_s, need_s)
         if not need_s:
-            return None, gx, None, None, None, None, None
+            return None, gx, None, None, None, None, None, None
         N, E = plan.n_dst, plan.num_edges
         ds = torch.empty(E, dtype=torch.float32, device=g.device)
         ds_self = torch.empty(N, dtype=torch.float32, device=g.device)
         dsq = torch.empty(N, dtype=torch.float32, device=g.device)
-        L.check(lib.tfgx_asap_attend_backward_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(sq), L.ptr(sh), L.ptr(bias),
-                                                  L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds), L.ptr(dp.contiguous()),
-                                                  L.ptr(dps.contiguous()), L.ptr(ds), L.ptr(ds_self), L.ptr(dsq),
-                                                  L.stream_ptr()), "tfgx_asap_attend_backward_f32")
+        if ctx.skip:      # the fixed-shape route: the centred form, exact for a row of one term (include/tfgx_asap_static.h)
+            L.check(lib.tfgx_asapstatic_attend_backward_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(sq), L.ptr(sh),
+                                                            L.ptr(bias), L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds),
+                                                            L.ptr(dp.contiguous()), L.ptr(dps.contiguous()), 1, L.ptr(ds),
+                                                            L.ptr(ds_self), L.ptr(dsq), L.stream_ptr()),
+                    "tfgx_asapstatic_attend_backward_f32")
+        else:
+            L.check(lib.tfgx_asap_attend_backward_f32(L.ptr(plan.row_ptr), L.ptr(plan.col), N, E, L.ptr(sq), L.ptr(sh), L.ptr(bias),
+                                                      L.ptr(p), L.ptr(p_self), L.ptr(pd), L.ptr(pds), L.ptr(dp.contiguous()),
+                                                      L.ptr(dps.contiguous()), L.ptr(ds), L.ptr(ds_self), L.ptr(dsq),
+                                                      L.stream_ptr()), "tfgx_asap_attend_backward_f32")
         # d sh_j = sum of ds over the edges that point AT j, plus j's self edge: a segment sum on the transposed plan
         pt, t2d = _transposed(plan)
         ones = torch.ones((N, 1), dtype=torch.float32, device=g.device)
         dsh = segment_reduce(pt, ones, L.SUM, w_csr=_permute(ds, t2d) if E else ds, self_coef=ds_self)[:, 0]
-        return None, gx, dsq, dsh.contiguous(), dsq.sum().reshape(1), None, None
+        return None, gx, dsq, dsh.contiguous(), dsq.sum().reshape(1), None, None, None
 
 
 def asap_attend_composed(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
@@ -1646,14 +1663,21 @@ def asap_attend_composed(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
 ASAP_FUSED = True      # developer A/B switch: False sends every width down the composed route
 
 
-def asap_attend(plan, x, sq, sh, bias, drop_rate=0.0, seed=0):
+def asap_attend(plan, x, sq, sh, bias, drop_rate=0.0, seed=0, skip_self_loops=False):
     """(c [N, F], k p [E] in the plan's CSR order, k p of the self edges [N]) — the fused launch up to
-    TFGX_ASAP_MAX_FEATURES columns, the composed route past it.  sq, sh: [N]; bias: [1]."""
-    if ASAP_FUSED and int(x.shape[1]) <= L.ASAP_MAX_FEATURES:
+    TFGX_ASAP_MAX_FEATURES columns, the composed route past it.  sq, sh: [N]; bias: [1].  skip_self_loops (nn.asap_static): an
+    edge row == col is absent; seed may then be a device tensor (nn.conv.gat.new_drop_seed inside a capture).  That form has
+    the fused launch only."""
+    static = skip_self_loops or isinstance(seed, torch.Tensor)
+    if static and int(x.shape[1]) > L.ASAP_MAX_FEATURES:
+        raise ValueError("asap_attend: x has {} columns, the fused attention takes {} (TFGX_ASAP_MAX_FEATURES) and the "
+                         "fixed-shape route has no other".format(int(x.shape[1]), L.ASAP_MAX_FEATURES))
+    if static or (ASAP_FUSED and int(x.shape[1]) <= L.ASAP_MAX_FEATURES):
+        seed = seed if isinstance(seed, torch.Tensor) else int(seed)
         if needs_grad(x, sq, sh, bias):
-            return _AsapAttend.apply(plan, x, sq, sh, bias, float(drop_rate), int(seed))
+            return _AsapAttend.apply(plan, x, sq, sh, bias, float(drop_rate), seed, bool(skip_self_loops))
         c, p, p_self, pd, pds = asap_attend_forward(plan, x.detach(), sq.detach().contiguous(), sh.detach().contiguous(),
-                                                    bias.detach().contiguous(), drop_rate, seed)
+                                                    bias.detach().contiguous(), drop_rate, seed, skip_self_loops=skip_self_loops)
         return (c, p, p_self) if pd is None else (c, pd, pds)
     return asap_attend_composed(plan, x, sq, sh, bias, drop_rate, seed)
 

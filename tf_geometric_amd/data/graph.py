@@ -414,6 +414,9 @@ class StaticBatchGraph(BatchGraph):
         self.edge_id = None             # ... and pooled edge -> parent edge, -1 for a padded one
         self.edge_src = None            # a dense-pooled batch (nn.diff_pool_static): pooled edge -> its entry of S^T A S, or -1
         self._degree_bound = None       # a dense-pooled batch and what is pooled from it: the most edges of a live row (K)
+        self._node_bound = None         # ... and the most nodes of one graph (K; K_blk after nn.asap_static)
+        self.node_score = None          # an ASAP-pooled batch (nn.asap_static): the raw float32 cluster scores [parent n_cap]
+        self.asap_blocks = None         # ... and the blocks P [B K_blk, K_blk] of S^T A1 S its edges were read from (None: K_blk = 0)
 
     def max_degree(self):
         """A bound of the edges of a live row, in either direction: the store's largest in- / out-degree for a batch of the
@@ -421,6 +424,50 @@ class StaticBatchGraph(BatchGraph):
         if self._degree_bound is not None:
             return int(self._degree_bound)
         return max(self._store._max_degrees())
+
+    def max_graph_nodes(self):
+        """A bound of the nodes of one graph of the batch, host numbers only: the store's largest graph for a collated or
+        SAG-pooled batch, num_clusters after a dense pool, K_blk after nn.asap_static."""
+        if self._node_bound is not None:
+            return int(self._node_bound)
+        return int(self._store._max_graph_nodes())
+
+    def asap_pooled_capacities(self, k=None, ratio=None):
+        """StaticBatchCapacities of this batch pooled by nn.asap_static(k= / ratio=): host arithmetic, no device.
+
+        Graph g of n_g nodes keeps m_g = min(k, n_g) clusters, or min(n_g, int(ceilf(float32(n_g) * float32(ratio)))) — the
+        rule of tfgx_segment_topk.  Both are non-decreasing in n_g (a float32 product by a non-negative constant, a ceiling and
+        a minimum all are), so with n_max = max_graph_nodes() no graph keeps more than K_blk = rule(n_max) clusters; the float32
+        product is evaluated as the kernel evaluates it (one rounding), not bounded.
+
+            max_nodes = m_max of pooled_capacities(k / ratio)            (sum_g m_g <= m_max: DESIGN.md 2.27)
+            max_edges = K_blk * m_max
+
+        for the pooled graph of slot g is a subset of the m_g x m_g block, self-loops included, and
+        sum_g m_g^2 <= (max_g m_g) * sum_g m_g <= K_blk * m_max.  The sink degree d stays; sinks = max(1, ceil(max_edges / d)).
+        From one ASAP level to the next the edges shrink, as K_blk and m_max do; the first level's bound can exceed a sparse
+        parent's max_edges.  K_blk itself is asap_clusters_per_graph.
+        ValueError: what pooled_capacities refuses, sizes beyond int32."""
+        cap = self.capacities
+        m_max = int(self.pooled_capacities(k=k, ratio=ratio).max_nodes)            # validates k / ratio
+        K_blk = self.asap_clusters_per_graph(k=k, ratio=ratio)
+        B, d = int(cap.batch_size), int(cap.sink_degree)
+        max_edges = K_blk * m_max
+        sinks = max(1, -(-max_edges // d))
+        if m_max + sinks >= (1 << 31) - 1 or max_edges >= (1 << 31) - 1:
+            raise ValueError("asap_pooled_capacities: {} kept nodes + {} sinks, {} edges ({} clusters per graph at most) do not "
+                             "fit int32".format(m_max, sinks, max_edges, K_blk))
+        return type(cap)(B, m_max, max_edges, d, sinks, m_max + sinks, max_edges)
+
+    def asap_clusters_per_graph(self, k=None, ratio=None):
+        """K_blk: the most clusters nn.asap_static(k= / ratio=) keeps of one graph of this batch — the selection's rule applied
+        to max_graph_nodes(), in float32 exactly as the kernel does.  Host arithmetic."""
+        import math
+        self.pooled_capacities(k=k, ratio=ratio)                                    # validates k / ratio
+        n_max = self.max_graph_nodes()
+        if k is not None:
+            return min(int(k), n_max)
+        return min(n_max, int(math.ceil(float(np.float32(n_max) * np.float32(ratio)))))
 
     def dense_pooled_capacities(self, num_clusters, drop_diagonal=False):
         """StaticBatchCapacities of this batch pooled by nn.diff_pool_static / nn.min_cut_pool_static (drop_diagonal=True) into

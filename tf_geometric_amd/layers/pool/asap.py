@@ -4,6 +4,7 @@
 import torch
 
 from ...nn.pool.asap import asap
+from ...nn.pool.asap_static import asap_static
 from .._base import Layer
 
 
@@ -66,3 +67,18 @@ class ASAP(Layer):
                     self.le_conv_aggr_neighbor_kernel, None,
                     k=self.k, ratio=self.ratio, le_conv_activation=self.le_conv_activation,
                     drop_rate=self.drop_rate, training=training, cache=cache, seed=seed)
+
+    def pool_static(self, x, batch, training=None, seed=None):
+        """The layer on a StaticBatchGraph (GraphStore.collate_static's, or an earlier pool_static's): the pooled
+        StaticBatchGraph of nn.asap_static with this layer's weights (built on first use, as call builds them), k / ratio,
+        activation and drop_rate.  No host read; capturable."""
+        self._maybe_build([x])
+        return asap_static(x, batch,
+                           self.attention_gcn_kernel, self.attention_gcn_bias,
+                           self.attention_query_kernel, self.attention_query_bias,
+                           self.attention_score_kernel, self.attention_score_bias,
+                           self.le_conv_self_kernel, self.le_conv_self_bias,
+                           self.le_conv_aggr_self_kernel, self.le_conv_aggr_self_bias,
+                           self.le_conv_aggr_neighbor_kernel,
+                           k=self.k, ratio=self.ratio, le_conv_activation=self.le_conv_activation,
+                           drop_rate=self.drop_rate, training=training, seed=seed)

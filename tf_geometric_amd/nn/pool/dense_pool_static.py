@@ -186,6 +186,7 @@ def _coarsen_static(what, car, x, adjacency_weight, S, K, drop_diagonal, bias=No
     pooled._store, pooled.graph_row_ptr = car.store, pooled_row_ptr
     pooled.node_index, pooled.edge_src = node_index, edge_src
     pooled._degree_bound = K                                    # a pooled row holds at most K edges, whatever the dataset's degrees
+    pooled._node_bound = K                                      # ... and a pooled graph exactly K nodes
     attach_static_plans(pooled, car.store, plans, arange, K)
     return pooled
 

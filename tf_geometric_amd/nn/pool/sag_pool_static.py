@@ -68,7 +68,14 @@ def topk_pool_static(batch, score, k=None, ratio=None, capacities=None):
     hold does not matter.  `capacities`: batch.pooled_capacities(k, ratio) when None."""
     what = "topk_pool_static"
     _static_batch(batch, what)
-    cap = _pooled_capacities(batch, capacities, k, ratio, what)
+    return select_static(batch, score, k, ratio, _pooled_capacities(batch, capacities, k, ratio, what), what)
+
+
+def select_static(batch, score, k, ratio, cap, what):
+    """The two launches of the selection at the pooled capacities `cap` (max_nodes, n_cap and sinks are read; nn.asap_static
+    brings capacities whose edges and sinks are not the parent's): a StaticTopK.  tfgx_static_pool_select takes ONE sink count
+    and uses it only to hold the live totals to n_cap - sinks and n_cap' - sinks: the smaller of the two counts keeps both
+    bounds inside the arrays and at or above max_nodes (a SAG level has the parent's sinks: nothing changes for it)."""
     lib = L.require_gpu()
     parent = batch.capacities
     B, n_cap = parent.batch_size, parent.n_cap
@@ -85,8 +92,8 @@ def topk_pool_static(batch, score, k=None, ratio=None, capacities=None):
     L.check(lib.tfgx_static_pool_table(L.ptr(batch.graph_row_ptr), L.ptr(batch.counts), B, -1 if k is None else int(k),
                                        0.0 if ratio is None else float(ratio), cap.max_nodes, cap.n_cap, L.ptr(pooled_row_ptr),
                                        L.ptr(counts), stream), "tfgx_static_pool_table")
-    L.check(lib.tfgx_static_pool_select(L.ptr(sc), L.ptr(batch.graph_row_ptr), L.ptr(pooled_row_ptr), B, n_cap, parent.sinks,
-                                        cap.n_cap, L.ptr(node_index), L.ptr(ngi), L.ptr(node_map), stream),
+    L.check(lib.tfgx_static_pool_select(L.ptr(sc), L.ptr(batch.graph_row_ptr), L.ptr(pooled_row_ptr), B, n_cap,
+                                        min(parent.sinks, cap.sinks), cap.n_cap, L.ptr(node_index), L.ptr(ngi), L.ptr(node_map), stream),
             "tfgx_static_pool_select")
     return StaticTopK(node_index, node_map, pooled_row_ptr, ngi, counts, cap)
 
@@ -172,7 +179,7 @@ def sag_pool_static(x, batch, score_gnn, k=None, ratio=None, score_activation=No
                               batch._store_len, given_ids=batch._given_ids)
     pooled._store, pooled.graph_row_ptr = store, sel.pooled_row_ptr
     pooled.node_index, pooled.edge_id = sel.node_index, edge_id
-    pooled._degree_bound = batch._degree_bound
+    pooled._degree_bound, pooled._node_bound = batch._degree_bound, batch._node_bound
     # no pooled row is longer than its parent row, and a sink holds sink_degree edges as before: the rule of collate_static
     attach_static_plans(pooled, store, plans, arange, batch.max_degree())
     return pooled
